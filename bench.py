@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path named by BASELINE.json: batched MPC / MHE / Kalman / GP steps per second.
 
-    python bench.py --gpus N --steps K --warmup W [--config C2]
+    python bench.py --gpus N --steps K --warmup W [--config C2] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -30,7 +30,16 @@ job, inputs resident in HBM.
 Every line carries
   roofline      the dominant kernel against the roof that bounds it: algorithmic flops (solves, GP) or
                 algorithmic bytes (filters) per launch / the HIP-event time of that launch on the stream it runs on
-  cpu_baseline  (N = 1 only) the oracle's CPU restatement of the same computation on a bounded sample of the same workload
+
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds what takes runs of its own:
+  cpu_baseline  (N = 1 only, unless --no-cpu-baseline) the oracle's CPU restatement of the same computation on a bounded sample
+                of the same workload
+  settled_loop  (C2) the same closed loop continued for 50 more steps after the timed region
+  single_instance_latency_us  (C1, in `config`) one QP solved alone, 20 timed calls
+
+`--dump-outputs DIR` writes what the timed path computed in its last timed step - the arrays its caller receives - as
+DIR/<name>.npy (float64; integer results converted).  The inputs are seeded, so two builds run with the same arguments can be
+compared output for output.  Above 64 MB in all, every array keeps the same fixed, seeded sample of instances.
 """
 import argparse
 import json
@@ -149,7 +158,8 @@ def pmc_issue(tag_key, kernel_key=None, kernel_ms=None):
 
 # ---------------------------------------------------------------------------------------------------------------------
 # workloads: each returns dict(step=callable, events=list filled by step, finish=callable -> (extra config, roofline dict),
-#                              units=instances per step on this rank, cpu=callable -> cpu_baseline dict)
+#                              units=instances per step on this rank, cpu=callable -> cpu_baseline dict,
+#                              outputs=callable -> {name: (tensor, instance axis)} of the last step, for --dump-outputs)
 # ---------------------------------------------------------------------------------------------------------------------
 def _events(torch, n):
     return [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n)]
@@ -540,7 +550,14 @@ def wl_nmpc(cfg, args, torch, dev, rank, world):
             Xtr, _ = P.c4_training_data()
             set_gp(Xtr, post.alpha, P.C4_GP['length_scales'], P.C4_GP['signal_variance'])
             return cpu_baseline_c2(spec, nst=10, slsqp=False, pb=pb, label='C4 (200 kernel terms per right-hand side)', per_thread=8)
-    return dict(step=step, finish=finish, units=B, cpu=cpu, unit="steps/s",
+
+    def outputs():
+        # what the closed loop hands its caller (the gathered rows of all shards), the shard's advanced plant states and the solution
+        g, sol = loop.last, nmpc._nlp_solution
+        out = {'u0': (g.u0, 0), 'status': (g.status, 0), 'iters': (g.iters, 0), 'x_next': (loop.x, 0)}
+        out.update({'nlp_' + k: (sol[k], 0) for k in ('x', 'f', 'lam_g', 'kkt_error') if sol.get(k) is not None})
+        return out
+    return dict(step=step, finish=finish, units=B, cpu=cpu, outputs=outputs, unit="steps/s",
                 metric="MPC steps/sec (batched instances, whole node) at fixed (nx,nu,N)")
 
 
@@ -557,7 +574,7 @@ def wl_mhe(args, torch, dev, rank, world):
     mhe.estimate(x_arrival=torch.as_tensor(xa, device=dev))
     rng = np.random.default_rng(5 + rank)
     noise = torch.as_tensor(.01 * rng.normal(size=(64, B, 2)), device=dev)
-    ev, log, cnt = [], [], [0]
+    ev, log, cnt, last = [], [], [0], [None]
 
     def step(timed):
         k = cnt[0] % 64
@@ -565,7 +582,7 @@ def wl_mhe(args, torch, dev, rank, world):
         mhe.add_measurements(yd[:, -1] + noise[k], ud[:, -1])      # window shifts by one sample (device ring buffer)
         e = _events(torch, 1)[0]        # warm-up steps run the identical path (event creation included)
         e[0].record()
-        mhe.estimate()
+        last[0] = mhe.estimate()
         e[1].record()
         if timed:
             ev.append(e)
@@ -584,7 +601,13 @@ def wl_mhe(args, torch, dev, rank, world):
 
     def cpu():
         return cpu_leg_mhe(spec)
-    return dict(step=step, finish=finish, units=B, cpu=cpu, unit="steps/s",
+
+    def outputs():
+        (x_est, p_est), sol = last[0], mhe._nlp_solution
+        out = {'x_est': (x_est, 0), 'p_est': (p_est, 0)}
+        out.update({'nlp_' + k: (sol[k], 0) for k in ('x', 'f', 'lam_g', 'status', 'iter_count', 'kkt_error') if sol.get(k) is not None})
+        return out
+    return dict(step=step, finish=finish, units=B, cpu=cpu, outputs=outputs, unit="steps/s",
                 metric="MHE estimates/sec (batched instances, whole node) at fixed (nx,ny,N)")
 
 
@@ -670,7 +693,12 @@ def wl_kf(kind, args, torch, dev, rank, world):
 
     def cpu():
         return cpu_leg_kf(kind, K)
-    return dict(step=step, finish=finish, units=B * K, cpu=cpu, unit="steps/s",
+
+    def outputs():
+        # the call's solution: the sequences over its K sampling instants (K > 1: [K, B, ...]) or the one step's ([B, ...])
+        ax = 1 if K > 1 else 0
+        return {'x': (f.solution['x'], ax), 'P': (f.solution['P'], ax), 'y_pred': (f.solution['y'], ax)}
+    return dict(step=step, finish=finish, units=B * K, cpu=cpu, outputs=outputs, unit="steps/s",
                 metric="Kalman filter steps/sec (batched instances, whole node)")
 
 
@@ -681,12 +709,12 @@ def wl_gp(args, torch, dev, rank, world):
     rng = np.random.default_rng(3 + rank)
     Xq = torch.as_tensor(np.stack([rng.uniform(0, 40, m), rng.uniform(0, 4, m)]), device=dev)
     n, nf = 200, 2
-    ev = []
+    ev, last = [], [None]
 
     def step(timed):
         e = _events(torch, 1)[0]        # warm-up steps run the identical path (event creation included)
         e[0].record()
-        gp.predict(Xq)
+        last[0] = gp.predict(Xq)
         e[1].record()
         if timed:
             ev.append(e)
@@ -710,7 +738,11 @@ def wl_gp(args, torch, dev, rank, world):
 
     def cpu():
         return cpu_leg_gp(Xq[:, :1 << 16].cpu().numpy())
-    return dict(step=step, finish=finish, units=m, cpu=cpu, unit="predictions/s",
+
+    def outputs():
+        mean, var = last[0]
+        return {'mean': (mean, 1), 'var': (var, 1)}
+    return dict(step=step, finish=finish, units=m, cpu=cpu, outputs=outputs, unit="predictions/s",
                 metric="GP predictions/sec (query columns with variance, whole node)")
 
 
@@ -722,13 +754,13 @@ def wl_lmpc(args, torch, dev, rank, world):
     x = torch.as_tensor(rng.uniform(-4, 4, (B, 2)), device=dev)
     AdT = torch.as_tensor(np.array([[1., .5], [0., 1.]]).T.copy(), device=dev)       # the plant x+ = A x + B u, row vectors
     BdT = torch.as_tensor(np.array([[.125], [.5]]).T.copy(), device=dev)
-    ev, log, solved = [], [], []
+    ev, log, solved, last = [], [], [], [None]
 
     def step(timed):
         nonlocal x
         e = _events(torch, 1)[0]        # warm-up steps run the identical path (event creation included)
         e[0].record()
-        u = mpc.optimize(x)
+        u = last[0] = mpc.optimize(x)
         e[1].record()
         if timed:
             ev.append(e)
@@ -747,17 +779,20 @@ def wl_lmpc(args, torch, dev, rank, world):
         fl_it = (N_ * (7 / 3 * nx_ ** 3 + 4 * nx_ * nx_ * nu_ + 2 * nx_ * nu_ * nu_ + nu_ ** 3 / 3 + 8 * nx_ * nx_ + 8 * nx_ * nu_ + 2 * nu_ * nu_)
                  if staged else 2 * mq * mq * n + mq ** 3 / 3 + 4 * mq * mq + 6 * n * mq)
         tf = B * iters * fl_it / (kern_ms * 1e-3) / 1e12
-        one = product_lmpc('corrected')
-        x1 = torch.as_tensor(np.array([[1., 1.]]), device=dev)
-        for _ in range(3):
-            one.optimize(x1)
-        torch.cuda.synchronize(dev)
-        e1 = _events(torch, 20)
-        for a, b in e1:
-            a.record()
-            one.optimize(x1)
-            b.record()
-        torch.cuda.synchronize(dev)
+        latency = {}
+        if args.full:           # one QP alone: a run of its own
+            one = product_lmpc('corrected')
+            x1 = torch.as_tensor(np.array([[1., 1.]]), device=dev)
+            for _ in range(3):
+                one.optimize(x1)
+            torch.cuda.synchronize(dev)
+            e1 = _events(torch, 20)
+            for a, b in e1:
+                a.record()
+                one.optimize(x1)
+                b.record()
+            torch.cuda.synchronize(dev)
+            latency["single_instance_latency_us"] = float(np.mean([a.elapsed_time(b) for a, b in e1])) * 1e3
         roof = {"bound": "mfma", "achieved": tf, "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": tf / FP64_PEAK_TFLOPS,
                 "traffic": pmc_traffic_bytes('C1', kernel_ms=kern_ms), "traffic_source": pmc_traffic_bytes('C1', with_source=True, kernel_ms=kern_ms)[1],
                 "kernel": "qp_ocp_kernel<2, 1, 16>" if staged else "qp_solve_reg_kernel<32, 24>", "kernel_ms": kern_ms,
@@ -771,12 +806,18 @@ def wl_lmpc(args, torch, dev, rank, world):
                              "uniformly in [-4, 4]^2: about 5 % of these measured states cannot keep the box (infeasible QPs, reported "
                              "as status 3 after a few iterations - `frac_status_1` is the rest)",
                  "batch_per_gpu": B, "global_batch": B * world, "mean_qp_iters": iters, "frac_status_1": float((torch.stack(solved) == 1).double().mean().item()),
-                 "single_instance_latency_us": float(np.mean([a.elapsed_time(b) for a, b in e1])) * 1e3}
+                 **latency}
         return extra, roof, "weak"
 
     def cpu():
         return cpu_leg_qp(warmup=args.warmup, steps=args.steps)
-    return dict(step=step, finish=finish, units=B, cpu=cpu, unit="steps/s",
+
+    def outputs():
+        sol = mpc._nlp_solution
+        out = {'u0': (last[0], 0), 'x_next': (x, 0)}
+        out.update({'nlp_' + k: (sol[k], 0) for k in ('x', 'f', 'status', 'iter_count') if sol.get(k) is not None})
+        return out
+    return dict(step=step, finish=finish, units=B, cpu=cpu, outputs=outputs, unit="steps/s",
                 metric="LMPC steps/sec (batched QPs, whole node)")
 
 
@@ -825,6 +866,31 @@ def timed_region(wl, warmup, steps, world, dev):
     return elapsed, units
 
 
+DUMP_BYTES = 64 * 10 ** 6       # --dump-outputs: at most this much in all (float64)
+
+
+def dump_outputs(outputs, out_dir, rank=0, world=1, budget=DUMP_BYTES):
+    """Write `outputs` ({name: (tensor, instance axis)}, None entries skipped) as <out_dir>/<name>.npy in float64, one file set
+    per rank (`<name>_rank<r>.npy` when world > 1).  Above `budget` bytes in all (shared by the ranks), every array keeps the same
+    fraction of its instances: a fixed, seeded sample along its instance axis, the same rows for arrays of the same length."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    arrs = {k: v for k, v in outputs.items() if v[0] is not None}
+    total = sum(8 * t.numel() for t, _ in arrs.values())
+    frac = min(1.0, budget / world / max(total, 1))
+    paths = []
+    for name, (t, ax) in arrs.items():
+        t = torch.as_tensor(t)
+        if frac < 1.0:
+            n = t.shape[ax]
+            rows = np.sort(np.random.default_rng(0).choice(n, max(1, int(n * frac)), replace=False))
+            t = t.index_select(ax, torch.as_tensor(rows, device=t.device))
+        path = os.path.join(out_dir, f"{name}{f'_rank{rank}' if world > 1 else ''}.npy")
+        np.save(path, np.ascontiguousarray(t.detach().to(torch.float64).cpu().numpy()))
+        paths.append(path)
+    return paths
+
+
 def respawn(args):
     """`python bench.py --gpus N` without a torchrun environment: one process per GPU under torch.distributed.run."""
     import socket
@@ -846,9 +912,15 @@ def main():
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--config', choices=CONFIGS, default='C2')
     ap.add_argument('--batch', type=int, default=0, help='instances per GPU (weak configs) / in total (C4, C5); 0 = the config default')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: leave the CPU baseline out')
     ap.add_argument('--kf-steps', type=int, default=16, help='C3-ekf / C3-ukf: filter steps per launch (1 = one launch per step)')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what takes runs of its own: CPU baseline, C2 settled loop, C1 single-instance latency')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write the last timed step's results as DIR/<name>.npy (float64, at most 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         sys.exit(respawn(args))
@@ -873,11 +945,13 @@ def main():
         torch.cuda.synchronize(dev)
 
     elapsed, units = timed_region(wl, args.warmup, args.steps, world, dev)
+    if args.dump_outputs:
+        dump_outputs(wl['outputs'](), args.dump_outputs, rank, world)
     extra, roof, scaling = wl['finish']()
     # the headline configuration's value moves with how far the closed loop has settled (fewer interior-point iterations per step
     # later on): the SAME loop continued for 50 more steps, timed the same way, is reported next to the driver's command
     settled = None
-    if args.config == 'C2':
+    if args.full and args.config == 'C2':
         sync()
         t1 = time.perf_counter()
         for _ in range(50):
@@ -900,7 +974,7 @@ def main():
             out["settled_loop"] = settled
         if 'hbm' in roof:
             out["roofline_hbm"] = dict(roof.pop('hbm'), bound="hbm", traffic=roof['traffic'])
-        if not args.no_cpu_baseline and world == 1:      # the CPU leg is timed at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:      # the CPU leg is timed at N = 1 only
             out["cpu_baseline"] = wl['cpu']()
         print(json.dumps(out))
     if world > 1:

@@ -15,12 +15,12 @@ for C in $CONFIGS; do
   OUT=$ROOT/gpurun_out/prof_$TAG/$C
   mkdir -p $OUT
   cd /tmp
-  BENCH="python $ROOT/bench.py --config $C --no-cpu-baseline"
+  BENCH="python $ROOT/bench.py --config $C --full --no-cpu-baseline"
   rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o $TAG -- $BENCH --steps $STEPS --warmup 5 > $OUT/bench_under_rocprof.log 2>&1
   rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -o $TAG -- $BENCH --steps 5 --warmup 2 > $OUT/pmc_fetch.log 2>&1
   rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write -o $TAG -- $BENCH --steps 5 --warmup 2 > $OUT/pmc_write.log 2>&1
   cd $ROOT
-  python bench.py --config $C --steps $STEPS --warmup 5 > $OUT/bench_n1.json 2> $OUT/bench_n1.err
+  python bench.py --config $C --full --steps $STEPS --warmup 5 > $OUT/bench_n1.json 2> $OUT/bench_n1.err
   # keep the merge-back small: only the csv files the summary reads
   find $OUT -name "*agent_info*" -delete
   tail -c 400 $OUT/bench_n1.json

@@ -16,8 +16,9 @@ profiles/run_pmc_valu.sh $TAG C5-dae 2 2 >> gpurun_out/pmc_$TAG.log 2>&1
 profiles/run_pmc_icache.sh $TAG >> gpurun_out/pmc_$TAG.log 2>&1      # instruction-cache hit rate of the headline kernel (87 KB of code)
 # the driver's command (20 steps) and a longer timed region (50 steps) of the headline configuration, and the batch sweep
 mkdir -p gpurun_out/bench_$TAG
-python bench.py --steps 20 --warmup 5 > gpurun_out/bench_$TAG/C2_20.json 2>/dev/null
-python bench.py --steps 50 --warmup 5 > gpurun_out/bench_$TAG/C2_50.json 2>/dev/null
+BENCH_OUT=$_      # (the directory just made)
+python bench.py --full --steps 20 --warmup 5 > $BENCH_OUT/C2_20.json 2>/dev/null
+python bench.py --full --steps 50 --warmup 5 > $BENCH_OUT/C2_50.json 2>/dev/null
 python bench.py --steps 20 --warmup 5 --batch 16384 --no-cpu-baseline > gpurun_out/bench_$TAG/C2_B16384.json 2>/dev/null
 python bench.py --config C3-ekf --batch 1048576 --no-cpu-baseline > gpurun_out/bench_$TAG/C3-ekf_B1M.json 2>/dev/null
 python bench.py --config C3-ukf --batch 1048576 --no-cpu-baseline > gpurun_out/bench_$TAG/C3-ukf_B1M.json 2>/dev/null

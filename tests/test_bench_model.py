@@ -166,3 +166,37 @@ def test_committed_counters_are_withheld_when_the_profiled_kernel_is_another_one
     iss, src = b.pmc_issue('C2', kernel_ms=ms * .4)
     assert iss is None and 'withheld' in src
     assert b._stale(None, 1.) is None and b._stale(1e6, 1.) is None and b._stale(1e6, 1.2) is None and 'withheld' in b._stale(1e6, 1.5)
+
+
+def test_dump_outputs_writes_float64_and_keeps_a_fixed_sample_under_the_budget(tmp_path):
+    """`bench.py --dump-outputs`: one float64 .npy per result (integer results converted, None entries skipped); above the budget
+    every array keeps the same seeded rows along its own instance axis, and the files stay within the budget."""
+    import numpy as np
+    import torch
+    b = _bench()
+    B = 1000
+    u = torch.arange(2 * B, dtype=torch.float64).reshape(B, 2)
+    st = torch.arange(B, dtype=torch.int32)
+    seq = torch.arange(3 * B * 4, dtype=torch.float64).reshape(3, B, 4)
+    outs = {'u0': (u, 0), 'status': (st, 0), 'x': (seq, 1), 'p': (None, 0)}
+    full = b.dump_outputs(outs, str(tmp_path / 'all'))
+    assert sorted(os.path.basename(p) for p in full) == ['status.npy', 'u0.npy', 'x.npy']
+    got = {os.path.basename(p)[:-4]: np.load(p) for p in full}
+    assert all(a.dtype == np.float64 for a in got.values())
+    np.testing.assert_array_equal(got['u0'], u.numpy())
+    np.testing.assert_array_equal(got['status'], np.arange(B))
+    np.testing.assert_array_equal(got['x'], seq.numpy())
+    budget = 8 * (2 * B + B + 12 * B) // 4
+    part = b.dump_outputs(outs, str(tmp_path / 'part'), budget=budget)
+    again = b.dump_outputs(outs, str(tmp_path / 'again'), budget=budget)
+    assert sum(os.path.getsize(p) - 128 for p in part) <= budget
+    s = {os.path.basename(p)[:-4]: np.load(p) for p in part}
+    rows = s['status'].astype(int)
+    assert 0 < len(rows) < B and np.all(np.diff(rows) > 0)
+    np.testing.assert_array_equal(s['u0'], u.numpy()[rows])
+    np.testing.assert_array_equal(s['x'], seq.numpy()[:, rows])
+    for p, q in zip(part, again):
+        np.testing.assert_array_equal(np.load(p), np.load(q))
+    # one file set per rank when several ranks write, the budget shared among them
+    r1 = b.dump_outputs({'u0': (u, 0)}, str(tmp_path / 'ranks'), rank=1, world=2)
+    assert [os.path.basename(p) for p in r1] == ['u0_rank1.npy']

@@ -3,7 +3,7 @@
 cd "$(dirname "$0")/../.."
 export TMPDIR=/tmp
 d=gpurun_out/c1prof; rm -rf $d
-rocprofv3 --kernel-trace --stats --output-format csv -d $d -o p -- python bench.py --config C1 --no-cpu-baseline --steps 30 > $d.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $d -o p -- python bench.py --config C1 --full --no-cpu-baseline --steps 30 > $d.log 2>&1
 grep '^{"metric"' $d.log | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('line:', d['value'], d['ms_per_step'], d['roofline']['kernel_ms'], d['config']['single_instance_latency_us'])"
 python - "$(find $d -name '*kernel_stats.csv' | head -1)" "$(find $d -name '*kernel_trace.csv' | head -1)" <<'PY'
 import csv, sys
