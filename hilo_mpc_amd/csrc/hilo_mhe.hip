@@ -18,6 +18,7 @@
 #include "hilo_jit.h"
 #include "hilo_mhe_est.h"
 #include "hilo_mhe_policy.h"
+#include "hilo_ocp_setup.h"
 
 namespace hilo {
 
@@ -145,8 +146,7 @@ extern "C" int hilo_mhe_create(const hilo_mhe_desc* d, int device, hilo_mhe** ou
     lds = ev->lds_bytes(d->N);
   }
   if (lds > 160 * 1024) return fail(HILO_ENOTSUP, "horizon %d needs %zu B of LDS per instance (limit 163840)", d->N, lds);
-  hilo_mhe* h = new hilo_mhe();
-  memset(h, 0, sizeof(*h));
+  auto h = new_handle<hilo_mhe>(hilo_mhe_destroy);
   h->est = ev;
   h->device = device; h->model_id = d->model_id; h->nx = nx; h->nu = nu; h->np = np; h->ny = ny; h->N = d->N;
   h->gen = gen ? 1 : 0;
@@ -160,19 +160,7 @@ extern "C" int hilo_mhe_create(const hilo_mhe_desc* d, int device, hilo_mhe** ou
   h->use_jit = jit ? 1 : 0;
   h->coll_d = D;
   OcpConst& c = h->host;
-  memset(&c, 0, sizeof(c));
-  ocp_default_options(c);
-  c.N = d->N; c.Nc = d->N; c.order = d->erk_order >= 1 ? d->erk_order : 4; c.nsub = d->n_sub >= 1 ? d->n_sub : 1; c.dt = d->dt;
-  if (D) {
-    c.coll.d = D;
-    for (int i = 0; i < D * D; ++i) c.coll.A[i] = d->coll_A[i];
-    for (int i = 0; i <= D; ++i) { c.coll.Dc[i] = d->coll_D[i]; c.coll.Bq[i] = 0.0; }
-  }
-  if (d->max_iter > 0) c.max_iter = d->max_iter;
-  if (d->acceptable_iter > 0) c.acceptable_iter = d->acceptable_iter;
-  if (d->tol > 0) c.tol = d->tol;
-  if (d->acceptable_tol > 0) c.acceptable_tol = d->acceptable_tol;
-  if (d->mu_init > 0) c.mu_init = d->mu_init;
+  ocp_init_const(c, d, d->N, D, nullptr);
   for (int i = 0; i < nx; ++i) {
     c.sz[i] = d->x_scaling ? d->x_scaling[i] : 1.0;
     c.sz[nx + i] = d->w_scaling ? d->w_scaling[i] : 1.0;
@@ -184,15 +172,12 @@ extern "C" int hilo_mhe_create(const hilo_mhe_desc* d, int device, hilo_mhe** ou
     for (int i = 0; i < nx * nx; ++i) *q++ = d->Ww ? d->Ww[i] : 0.0;
     for (int i = 0; i < nu; ++i) *q++ = d->u_scaling ? d->u_scaling[i] : 1.0;
   }
-  const double relax = d->bound_relax_factor >= 0.0 ? d->bound_relax_factor : 1e-8;
-  c.bound_relax = relax;
   for (int i = 0; i < 2 * nx; ++i) {
     const double* lbs = i < nx ? d->x_lb : d->w_lb;
     const double* ubs = i < nx ? d->x_ub : d->w_ub;
     const int j = i < nx ? i : i - nx;
     double lb = lbs ? lbs[j] / c.sz[i] : -INFINITY, ub = ubs ? ubs[j] / c.sz[i] : INFINITY;
-    if (lb > -INFINITY) lb -= relax * fmax(1.0, fabs(lb));
-    if (ub < INFINITY) ub += relax * fmax(1.0, fabs(ub));
+    relax_box(lb, ub, c.bound_relax);
     HILO_REQUIRE(lb < ub, "hilo_mhe_create: empty box for variable %d", i);
     c.lbz[i] = lb; c.ubz[i] = ub;
   }
@@ -217,9 +202,8 @@ extern "C" int hilo_mhe_create(const hilo_mhe_desc* d, int device, hilo_mhe** ou
       for (int m = 0; m < OCP_MAXNC; ++m) { c.dlb[m] = -INFINITY; c.dub[m] = INFINITY; }
       for (int r = 0; r < nrow_pt; ++r) { c.cost[o_rowx + r] = row_expr[r]; c.cost[o_rref + r] = row_expr[r]; }
       for (int m = 0; m < nrow_all; ++m) {
-        const int r = m % nrow_pt;
-        c.dlb[m] = row_lb[r] > -INFINITY ? row_lb[r] - relax * fmax(1.0, fabs(row_lb[r])) : row_lb[r];
-        c.dub[m] = row_ub[r] < INFINITY ? row_ub[r] + relax * fmax(1.0, fabs(row_ub[r])) : row_ub[r];
+        c.dlb[m] = row_lb[m % nrow_pt]; c.dub[m] = row_ub[m % nrow_pt];
+        relax_box(c.dlb[m], c.dub[m], c.bound_relax);
         c.row_ref[m] = (short)m;
       }
       c.nc = nrow_all; c.nc_term = 0; c.n_con_ref = nrow_all; c.n_tcon_ref = 0;   // compact multipliers; the output pass orders them
@@ -232,15 +216,14 @@ extern "C" int hilo_mhe_create(const hilo_mhe_desc* d, int device, hilo_mhe** ou
     for (int j = 0; j < np; ++j) {
       const double sp = d->p_scaling ? d->p_scaling[j] : 1.0;
       double pl = d->p_lb ? d->p_lb[j] / sp : -INFINITY, pu = d->p_ub ? d->p_ub[j] / sp : INFINITY;
-      if (!(pl <= pu)) { delete h; return fail(HILO_EINVAL, "hilo_mhe_create: p_lb > p_ub for parameter %d", j); }
+      HILO_REQUIRE(pl <= pu, "hilo_mhe_create: p_lb > p_ub for parameter %d", j);
       const bool estimated = d->estimate_parameters && pl < pu;
       c.sz[nx + j] = sp;
       c.k0_only_mask |= 1u << (nx + j);                         // one box (and one barrier term) per parameter
       if (estimated) {
         c.x0_free_mask |= 1u << (nx + j);
         h->est_mask |= 1u << j;
-        if (pl > -INFINITY) pl -= relax * fmax(1.0, fabs(pl));
-        if (pu < INFINITY) pu += relax * fmax(1.0, fabs(pu));
+        relax_box(pl, pu, c.bound_relax);
         c.lbz[nx + j] = pl; c.ubz[nx + j] = pu;
       } else {
         c.lbz[nx + j] = -INFINITY; c.ubz[nx + j] = INFINITY;   // pinned through x_0 (IPOPT: fixed variable removed)
@@ -256,52 +239,42 @@ extern "C" int hilo_mhe_create(const hilo_mhe_desc* d, int device, hilo_mhe** ou
     rq.mhe_gen = gen; rq.mhe_noise = has_noise;
     rq.has_fun = d->n_con > 0; rq.nc = nrow_all;
     rc = jit_nmpc_kernels(rq, device, &h->jit);
-    if (!rc && getenv("HILO_JIT_COMPILE_ONLY")) { delete h; return HILO_COMPILED_ONLY; }   // cache warmed, no handle
+    if (!rc && getenv("HILO_JIT_COMPILE_ONLY")) return HILO_COMPILED_ONLY;   // cache warmed, no handle
     if (!rc && (h->jit.dims[0] != nx || h->jit.dims[1] != nu || h->jit.dims[2] != np || h->jit.dims[3] != ny))
       rc = fail(HILO_EINVAL, "hilo_mhe_create: the compiled model has (nx, nu, np, ny) = (%d, %d, %d, %d); the description says "
                              "(%d, %d, %d, %d)", h->jit.dims[0], h->jit.dims[1], h->jit.dims[2], h->jit.dims[3], nx, nu, np, ny);
     if (!rc && gen && h->jit.dims[6] != nx + np)
       rc = fail(HILO_EINVAL, "hilo_mhe_create: the compiled general estimator has %d engine states, expected %d", h->jit.dims[6], nx + np);
-    if (rc) { delete h; return rc; }
+    if (rc) return rc;
     h->lds_bytes = (size_t)h->jit.dims[5];
   }
-  hipError_t e = hipSetDevice(device);
-  if (e == hipSuccess) e = hipMalloc((void**)&h->dev, sizeof(OcpConst));
-  if (e == hipSuccess) e = hipMemcpy(h->dev, &c, sizeof(OcpConst), hipMemcpyHostToDevice);
-  if ((ev || gen) && e == hipSuccess) {
-    // tiled guess in engine layout: [x_guess | p_guess] per stage, w_guess (mhe.py:620, :633-649)
-    const int nxa = nx + np, nve = (d->N + 1) * nxa + (has_noise ? d->N * nx : 0);
-    double* g = new double[nve];
+  // tiled guess in engine layout: [x_guess | p_guess] per stage, w_guess (mhe.py:620, :633-649)
+  const int nxa = nx + np, nve = (d->N + 1) * nxa + (has_noise ? d->N * nx : 0);
+  std::vector<double> ge;
+  if (ev || gen) {
+    ge.resize(nve);
     for (int k = 0; k <= d->N; ++k) {
-      for (int i = 0; i < nx; ++i) g[k * nxa + i] = (d->x_guess ? d->x_guess[i] : 0.0) / c.sz[i];
-      for (int j = 0; j < np; ++j) g[k * nxa + nx + j] = (d->p_guess ? d->p_guess[j] : 0.0) / c.sz[nx + j];
+      for (int i = 0; i < nx; ++i) ge[k * nxa + i] = (d->x_guess ? d->x_guess[i] : 0.0) / c.sz[i];
+      for (int j = 0; j < np; ++j) ge[k * nxa + nx + j] = (d->p_guess ? d->p_guess[j] : 0.0) / c.sz[nx + j];
     }
     for (int k = 0; k < d->N && has_noise; ++k)
-      for (int i = 0; i < nx; ++i) g[(d->N + 1) * nxa + k * nx + i] = (d->w_guess ? d->w_guess[i] : 0.0) / c.sz[nxa + i];
-    e = hipMalloc((void**)&h->v_guess_e, sizeof(double) * nve);
-    if (e == hipSuccess) e = hipMemcpy(h->v_guess_e, g, sizeof(double) * nve, hipMemcpyHostToDevice);
-    delete[] g;
+      for (int i = 0; i < nx; ++i) ge[(d->N + 1) * nxa + k * nx + i] = (d->w_guess ? d->w_guess[i] : 0.0) / c.sz[nxa + i];
   }
   // tiled guess row; the run-time compiled kernel reads every start row behind a parameter prefix ([p | x | w]), the
   // zoo kernels take the guess without one
   const int gpre = jit ? np : 0;
   const int nvf = gpre + (d->N + 1) * nx + d->N * nx;      // (read by the plain policies only; they always have the noise block)
-  if (e == hipSuccess) e = hipMalloc((void**)&h->v_guess, sizeof(double) * nvf);
-  if (e == hipSuccess) {
-    double* g = new double[nvf];  // mhe.py:633-649: tiled guesses, scaled (mhe.py:229-236)
-    for (int i = 0; i < gpre; ++i) g[i] = 0.0;
-    for (int k = 0; k <= d->N; ++k)
-      for (int i = 0; i < nx; ++i) g[gpre + k * nx + i] = (d->x_guess ? d->x_guess[i] : 0.0) / c.sz[i];
-    for (int k = 0; k < d->N; ++k)
-      for (int i = 0; i < nx; ++i) g[gpre + (d->N + 1) * nx + k * nx + i] = (d->w_guess ? d->w_guess[i] : 0.0) / c.sz[nx + i];
-    e = hipMemcpy(h->v_guess, g, sizeof(double) * nvf, hipMemcpyHostToDevice);
-    delete[] g;
-  }
-  if (e != hipSuccess) {
-    hilo_mhe_destroy(h);
-    return fail(HILO_EHIP, "hilo_mhe_create: %s", hipGetErrorString(e));
-  }
-  *out = h;
+  std::vector<double> g(nvf, 0.0);  // mhe.py:633-649: tiled guesses, scaled (mhe.py:229-236)
+  for (int k = 0; k <= d->N; ++k)
+    for (int i = 0; i < nx; ++i) g[gpre + k * nx + i] = (d->x_guess ? d->x_guess[i] : 0.0) / c.sz[i];
+  for (int k = 0; k < d->N; ++k)
+    for (int i = 0; i < nx; ++i) g[gpre + (d->N + 1) * nx + k * nx + i] = (d->w_guess ? d->w_guess[i] : 0.0) / c.sz[nx + i];
+  hipError_t e = hipSetDevice(device);
+  if (e == hipSuccess) e = ocp_upload(&h->dev, &c, sizeof(OcpConst));
+  if ((ev || gen) && e == hipSuccess) e = ocp_upload(&h->v_guess_e, ge.data(), sizeof(double) * nve);
+  if (e == hipSuccess) e = ocp_upload(&h->v_guess, g.data(), sizeof(double) * nvf);
+  if (e != hipSuccess) return fail(HILO_EHIP, "hilo_mhe_create: %s", hipGetErrorString(e));
+  *out = h.release();
   return HILO_OK;
 }
 
@@ -365,12 +338,9 @@ extern "C" int hilo_mhe_estimate(hilo_mhe* h, int64_t batch, const double* x_arr
   hipStream_t s = (hipStream_t)stream;
   const int wp = h->np + h->nx, ws = h->nu + h->ny;
   if (h->buf_batch != batch) {
-    if (h->par_buf) HILO_HIP_CHECK(hipFree(h->par_buf));
-    if (h->sd_buf) HILO_HIP_CHECK(hipFree(h->sd_buf));
-    h->par_buf = h->sd_buf = nullptr;
-    hipError_t e = hipMalloc((void**)&h->par_buf, sizeof(double) * (size_t)wp * batch);
-    if (e == hipSuccess) e = hipMalloc((void**)&h->sd_buf, sizeof(double) * (size_t)(h->N + 1) * ws * batch);
-    if (e != hipSuccess) return fail(HILO_ENOMEM, "MHE buffers: %s", hipGetErrorString(e));
+    int rc = batch_realloc(&h->par_buf, sizeof(double) * (size_t)wp * batch, "MHE buffers: %s");
+    if (!rc) rc = batch_realloc(&h->sd_buf, sizeof(double) * (size_t)(h->N + 1) * ws * batch, "MHE buffers: %s");
+    if (rc) return rc;
     h->buf_batch = batch;
   }
   {
@@ -385,10 +355,8 @@ extern "C" int hilo_mhe_estimate(hilo_mhe* h, int64_t batch, const double* x_arr
       double** bufs[] = {&h->x0e, &h->v0e, &h->ve, &h->lame, &h->v_warm};
       const size_t sizes[] = {(size_t)nxa, (size_t)nve, (size_t)nve, (size_t)h->N * (nxa + h->nc), (size_t)h->n_v};
       for (int q = 0; q < 5; ++q) {
-        if (*bufs[q]) HILO_HIP_CHECK(hipFree(*bufs[q]));
-        *bufs[q] = nullptr;
-        hipError_t e = hipMalloc((void**)bufs[q], sizeof(double) * sizes[q] * batch);
-        if (e != hipSuccess) return fail(HILO_ENOMEM, "MHE buffers: %s", hipGetErrorString(e));
+        const int rc = batch_realloc(bufs[q], sizeof(double) * sizes[q] * batch, "MHE buffers: %s");
+        if (rc) return rc;
       }
       h->warm_batch = batch;
       h->warm_valid = 0;
@@ -439,12 +407,9 @@ extern "C" int hilo_mhe_estimate(hilo_mhe* h, int64_t batch, const double* x_arr
     double *vdst = v_opt, *ldst = lam_g;
     if (h->coll_d) {   // the engine's result goes to buffers of the handle; the output pass writes the reference's layout
       if (!h->vc || h->vc_batch != batch || !h->lamc) {
-        if (h->vc) HILO_HIP_CHECK(hipFree(h->vc));
-        if (h->lamc) HILO_HIP_CHECK(hipFree(h->lamc));
-        h->vc = h->lamc = nullptr;
-        hipError_t e = hipMalloc((void**)&h->vc, sizeof(double) * (size_t)h->n_vc * batch);
-        if (e == hipSuccess) e = hipMalloc((void**)&h->lamc, sizeof(double) * (size_t)h->N * h->nx * batch);
-        if (e != hipSuccess) return fail(HILO_ENOMEM, "MHE buffers: %s", hipGetErrorString(e));
+        rc = batch_realloc(&h->vc, sizeof(double) * (size_t)h->n_vc * batch, "MHE buffers: %s");
+        if (!rc) rc = batch_realloc(&h->lamc, sizeof(double) * (size_t)h->N * h->nx * batch, "MHE buffers: %s");
+        if (rc) return rc;
         h->vc_batch = batch;
       }
       vdst = h->vc; ldst = h->lamc;
@@ -468,10 +433,8 @@ extern "C" int hilo_mhe_estimate(hilo_mhe* h, int64_t batch, const double* x_arr
     HILO_HIP_CHECK(hipMemcpy2DAsync(v_opt, sizeof(double) * h->n_v, h->par_buf, sizeof(double) * wp,
                                     sizeof(double) * h->np, batch, hipMemcpyDeviceToDevice, s));
   if (h->warm_batch != batch) {
-    if (h->v_warm) HILO_HIP_CHECK(hipFree(h->v_warm));
-    h->v_warm = nullptr;
-    hipError_t e = hipMalloc((void**)&h->v_warm, sizeof(double) * h->n_v * batch);
-    if (e != hipSuccess) return fail(HILO_ENOMEM, "warm-start buffer: %s", hipGetErrorString(e));
+    rc = batch_realloc(&h->v_warm, sizeof(double) * h->n_v * batch, "warm-start buffer: %s");
+    if (rc) return rc;
     h->warm_batch = batch;
   }
   HILO_HIP_CHECK(hipMemcpyAsync(h->v_warm, v_opt, sizeof(double) * h->n_v * batch, hipMemcpyDeviceToDevice, s));

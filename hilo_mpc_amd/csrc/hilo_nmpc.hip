@@ -45,6 +45,7 @@ __global__ void plant_step_kernel(const OcpConst* __restrict__ pcg, int64_t batc
 using namespace hilo;
 
 #include "hilo_nmpc_handle.h"
+#include "hilo_ocp_setup.h"
 
 #define HILO_NMPC_MODELS(X)              \
   X(HILO_MODEL_CHEMOSTAT4, Chemostat4)   \
@@ -79,10 +80,6 @@ extern "C" void hilo_nmpc_destroy(hilo_nmpc* h) {
   if (h->vc) (void)hipFree(h->vc);
   if (h->lamc) (void)hipFree(h->lamc);
   delete h;
-}
-
-static void copy_or(double* dst, const double* src, int n, double dflt) {
-  for (int i = 0; i < n; ++i) dst[i] = src ? src[i] : dflt;
 }
 
 extern "C" int hilo_nmpc_create(const hilo_nmpc_desc* d, int device, hilo_nmpc** out) {
@@ -129,72 +126,30 @@ extern "C" int hilo_nmpc_create(const hilo_nmpc_desc* d, int device, hilo_nmpc**
                               "compile the problem at run time (desc.user_source, user_policy 2)", GEN_NEXPR, d->n_con, d->n_tcon);
   const bool general = d->n_path_var > 0 || d->n_con > 0 || d->n_tcon > 0;
   const GenVariant* gv = nullptr;
-  int nth = 0, ne = 0, nrow = 0, n_con_ref = 0;
-  int row_expr[OCP_MAXNC], row_sign[OCP_MAXNC], row_e[OCP_MAXNC], row_ref[OCP_MAXNC];
-  int ntrow = 0, n_tcon_ref = 0, ne_stage = 0;   // terminal rows of the engine / of the reference's g; slacks of the stage constraint
-  int trow_expr[OCP_MAXNC], trow_sign[OCP_MAXNC], trow_e[OCP_MAXNC], trow_ref[OCP_MAXNC];
-  double trow_lb[OCP_MAXNC], trow_ub[OCP_MAXNC];
-  double row_lb[OCP_MAXNC], row_ub[OCP_MAXNC];
+  int nth = 0, ne = 0;
+  OcpRows rows, trows;   // stage / terminal rows of the engine
   if (general) {
     if (d->learned) return fail(HILO_ENOTSUP, "a learned term together with path following / stage constraints is not built");
     nth = d->n_path_var;
-    if (d->n_con > 0) {
-      HILO_REQUIRE(d->con_prog && d->con_prog_len > 0, "hilo_nmpc_create: n_con > 0 but no constraint program");
-      ne = d->con_soft ? d->n_con : 0;
-      n_con_ref = d->con_soft ? 2 * d->n_con : d->n_con;   // rows per stage in the reference's g (mpc.py:1711-1712)
-      for (int j = 0; j < d->n_con; ++j) {
-        const double lb = d->con_lb ? d->con_lb[j] : -INFINITY, ub = d->con_ub ? d->con_ub[j] : INFINITY;
-        HILO_REQUIRE(lb <= ub, "hilo_nmpc_create: constraint %d has lb > ub", j);
-        if (d->con_soft) {   // c - e <= ub | -c - e <= -lb; a row without a finite bound constrains nothing and is dropped
-          if (ub < INFINITY) {
-            HILO_REQUIRE(nrow < OCP_MAXNC, "too many constraint rows");
-            row_expr[nrow] = j; row_sign[nrow] = 1; row_e[nrow] = j; row_lb[nrow] = -INFINITY; row_ub[nrow] = ub;
-            row_ref[nrow++] = j;
-          }
-          if (lb > -INFINITY) {
-            HILO_REQUIRE(nrow < OCP_MAXNC, "too many constraint rows");
-            row_expr[nrow] = j; row_sign[nrow] = -1; row_e[nrow] = j; row_lb[nrow] = -INFINITY; row_ub[nrow] = -lb;
-            row_ref[nrow++] = d->n_con + j;
-          }
-        } else if (lb > -INFINITY || ub < INFINITY) {
-          HILO_REQUIRE(nrow < OCP_MAXNC, "too many constraint rows");
-          row_expr[nrow] = j; row_sign[nrow] = 1; row_e[nrow] = -1; row_lb[nrow] = lb; row_ub[nrow] = ub;
-          row_ref[nrow++] = j;
-        }
-      }
-    }
-    ne_stage = ne;
+    if (d->n_con > 0) HILO_REQUIRE(d->con_prog && d->con_prog_len > 0, "hilo_nmpc_create: n_con > 0 but no constraint program");
+    rc = nmpc_stage_rows(d, rows);
+    if (rc) return rc;
     if (d->n_tcon > 0) {
       HILO_REQUIRE(d->tcon_prog && d->tcon_prog_len > 0, "hilo_nmpc_create: n_tcon > 0 but no terminal constraint program");
-      if (d->tcon_soft) {
-        if (ne_stage > 0 || d->n_tcon != 1)
-          return fail(HILO_ENOTSUP, "one shared slack in this build: a soft terminal constraint needs n_tcon = 1 and a hard (or "
-                                    "no) stage constraint");
-        ne += d->n_tcon;
-      }
-      n_tcon_ref = d->tcon_soft ? 2 * d->n_tcon : d->n_tcon;   // mpc.py:1687-1690 / :1696-1698
-      for (int j = 0; j < d->n_tcon; ++j) {
-        const double lb = d->tcon_lb ? d->tcon_lb[j] : -INFINITY, ub = d->tcon_ub ? d->tcon_ub[j] : INFINITY;
-        HILO_REQUIRE(lb <= ub, "hilo_nmpc_create: terminal constraint %d has lb > ub", j);
-        auto add = [&](int sign, int e, double rlb, double rub, int ref) {
-          trow_expr[ntrow] = j; trow_sign[ntrow] = sign; trow_e[ntrow] = e; trow_lb[ntrow] = rlb; trow_ub[ntrow] = rub;
-          trow_ref[ntrow++] = ref;
-        };
-        HILO_REQUIRE(nrow + ntrow + (d->tcon_soft ? (ub < INFINITY) + (lb > -INFINITY) : 1) <= OCP_MAXNC, "too many constraint rows");
-        if (d->tcon_soft) {   // same row pair as the soft stage constraint; the slack index counts after the stage slacks
-          if (ub < INFINITY) add(1, ne_stage + j, -INFINITY, ub, j);
-          if (lb > -INFINITY) add(-1, ne_stage + j, -INFINITY, -lb, d->n_tcon + j);
-        } else {
-          add(1, -1, lb, ub, j);
-        }
-      }
+      if (d->tcon_soft && (rows.nslack > 0 || d->n_tcon != 1))
+        return fail(HILO_ENOTSUP, "one shared slack in this build: a soft terminal constraint needs n_tcon = 1 and a hard (or "
+                                  "no) stage constraint");
     }
-    gv = nmpc_gen_find(d->model_id, nth, ne, nrow + ntrow, d->N);
+    rc = nmpc_term_rows(d, rows.nslack, rows.n, trows);
+    if (rc) return rc;
+    ne = rows.nslack + trows.nslack;
+    gv = nmpc_gen_find(d->model_id, nth, ne, rows.n + trows.n, d->N);
     if (!gv)
       return fail(HILO_ENOTSUP, "no device instantiation for model %d with %d path variable(s), %d shared slack(s) and %d "
-                                "inequality row(s) per stage at horizon %d in this build", d->model_id, nth, ne, nrow + ntrow, d->N);
+                                "inequality row(s) per stage at horizon %d in this build", d->model_id, nth, ne, rows.n + trows.n, d->N);
     lds = gv->lds_bytes(d->N);
   }
+  const int ne_stage = rows.nslack;
   const CollVariant* cv = nullptr;
   if (d->collocation_degree > 0) {
     if (general || d->learned)
@@ -225,8 +180,7 @@ extern "C" int hilo_nmpc_create(const hilo_nmpc_desc* d, int device, hilo_nmpc**
   // engine dimensions: [model x | theta | e], [model u | u_theta]
   const int nxe = gv ? gv->nx : nx, nue = gv ? gv->nu : nu, nxv = gv ? gv->nxv : nx;
   const int nz = nxe + nue;
-  hilo_nmpc* h = new hilo_nmpc();
-  memset(h, 0, sizeof(*h));
+  auto h = new_handle<hilo_nmpc>(hilo_nmpc_destroy);
   h->device = device; h->model_id = d->model_id; h->nx = nx; h->nu = nu; h->np = np; h->N = d->N;
   h->gen = gv; h->nu_out = nu;
   h->jit_policy = -1;
@@ -235,42 +189,19 @@ extern "C" int hilo_nmpc_create(const hilo_nmpc_desc* d, int device, hilo_nmpc**
   h->tv = tvv;
   h->big = bigv;
   h->n_vc = (d->N + 1) * nx + d->N * nu;
-  const int dn = cv ? cv->degree * nx : 0;
+  const int D = cv ? cv->degree : 0, dn = D * nx;
   h->n_v = (d->N + 1) * nxv + d->N * nue + ne + d->N * dn;   // mpc.py:1440-1443 (+ the soft-constraint slack, :1529-1537)
-  h->n_g = d->N * (nxv + n_con_ref + dn) + (general ? n_tcon_ref : 0);   // mpc.py:1657-1669, :1684-1725
+  h->n_g = d->N * (nxv + rows.nref + dn) + trows.nref;     // mpc.py:1657-1669, :1684-1725
   h->lds_bytes = lds;
   OcpConst& c = h->host;
-  memset(&c, 0, sizeof(c));
-  ocp_default_options(c);
-  c.N = d->N; c.Nc = d->N; c.order = d->erk_order >= 1 ? d->erk_order : 4; c.nsub = d->n_sub >= 1 ? d->n_sub : 1;
-  c.dt = d->dt;
+  ocp_init_const(c, d, d->N, D, nullptr);
   c.flags = 1;  // lam_g in the reference's convention (terminal cost on Phi_{N-1}, mpc.py:1682)
-  if (cv) {
-    c.coll.d = cv->degree;
-    for (int i = 0; i < cv->degree * cv->degree; ++i) c.coll.A[i] = d->coll_A[i];
-    for (int i = 0; i <= cv->degree; ++i) c.coll.Dc[i] = d->coll_D[i];
-  }
-  if (d->max_iter > 0) c.max_iter = d->max_iter;
-  if (d->acceptable_iter > 0) c.acceptable_iter = d->acceptable_iter;
-  double sx[OCP_MAXNX], su[OCP_MAXNU];
-  copy_or(sx, d->x_scaling, nx, 1.0);
-  copy_or(su, d->u_scaling, nu, 1.0);
-  for (int i = 0; i < nz; ++i) c.sz[i] = 1.0;   // path variable, shared slack, virtual input: unit scaling (mpc.py:1200-1201)
-  for (int i = 0; i < nx; ++i) c.sz[i] = sx[i];
-  for (int i = 0; i < nu; ++i) c.sz[nxe + i] = su[i];
-  const double relax = d->bound_relax_factor >= 0.0 ? d->bound_relax_factor : 1e-8;
-  c.bound_relax = relax;
-  auto relaxed_lb = [&](double lb) { return lb > -INFINITY ? lb - relax * fmax(1.0, fabs(lb)) : lb; };
-  auto relaxed_ub = [&](double ub) { return ub < INFINITY ? ub + relax * fmax(1.0, fabs(ub)) : ub; };
+  if (d->max_hessian_perturbation > 0) c.delta_w_max = d->max_hessian_perturbation;
   if (!gv) {
     // cost block layout of NmpcTrack<M>: [Wz | zref | WN | xrefN | Wdu | has_du]
-    double* q = c.cost;
-    for (int i = 0; i < nz * nz; ++i) *q++ = d->Wz ? d->Wz[i] : 0.0;
-    for (int i = 0; i < nz; ++i) *q++ = d->zref ? d->zref[i] : 0.0;
-    for (int i = 0; i < nx * nx; ++i) *q++ = d->WN ? d->WN[i] : 0.0;
-    for (int i = 0; i < nx; ++i) *q++ = d->xrefN ? d->xrefN[i] : 0.0;
-    for (int i = 0; i < nu * nu; ++i) *q++ = d->Wdu ? d->Wdu[i] : 0.0;
-    *q++ = d->Wdu ? 1.0 : 0.0;
+    const int o_wn = nz * nz + nz, o_wdu = o_wn + nx * nx + nx;
+    pack_quad_cost(c.cost, {0, nz * nz, o_wn, o_wn + nx * nx, o_wdu, o_wdu + nu * nu, nx, nz, nx}, d, nx, nu, 0);
+    double* q = c.cost + o_wdu + nu * nu + 1;
     if ((q - c.cost) + nz * nz + nu * nu <= OCP_NCOST) {   // NmpcTrack<M>::SYMTAB: Sz = Wz + Wz^T, Sdu = Wdu + Wdu^T
       for (int i = 0; i < nz; ++i)
         for (int j = 0; j < nz; ++j) *q++ = d->Wz ? d->Wz[i * nz + j] + d->Wz[j * nz + i] : 0.0;
@@ -278,31 +209,12 @@ extern "C" int hilo_nmpc_create(const hilo_nmpc_desc* d, int device, hilo_nmpc**
         for (int j = 0; j < nu; ++j) *q++ = d->Wdu ? d->Wdu[i * nu + j] + d->Wdu[j * nu + i] : 0.0;
     }
   } else {
-    // cost block layout of NmpcGen (hilo_nmpc_gen.h); model z index -> engine z index
-    auto ez = [&](int i) { return i < nx ? i : nxe + (i - nx); };
-    const int mz = nx + nu;
-    for (int i = 0; i < mz; ++i) {
-      for (int j = 0; j < mz; ++j) c.cost[gv->o_wz + ez(i) * nz + ez(j)] = d->Wz ? d->Wz[i * mz + j] : 0.0;
-      c.cost[gv->o_zref + ez(i)] = d->zref ? d->zref[i] : 0.0;
-    }
-    for (int i = 0; i < nx; ++i) {
-      for (int j = 0; j < nx; ++j) c.cost[gv->o_wn + i * nxe + j] = d->WN ? d->WN[i * nx + j] : 0.0;
-      c.cost[gv->o_xrefn + i] = d->xrefN ? d->xrefN[i] : 0.0;
-    }
-    for (int i = 0; i < nu * nu; ++i) c.cost[gv->o_wdu + i] = d->Wdu ? d->Wdu[i] : 0.0;
-    c.cost[gv->o_hasdu] = d->Wdu ? 1.0 : 0.0;
-    if (nth && d->has_u_pf_ref) {   // mpc.py:1202-1204
-      const int iu = nxe + nu;
-      c.cost[gv->o_wz + iu * nz + iu] = d->u_pf_weight;
-      c.cost[gv->o_zref + iu] = d->u_pf_ref;
-    }
-    for (int a = 0; a < ne_stage; ++a)    // e^T W e once per stage (mpc.py:1708), W = 1e4 I by default (modeling.py:875)
-      for (int b = 0; b < ne_stage; ++b)
-        c.cost[gv->o_wz + (nx + nth + a) * nz + (nx + nth + b)] = d->con_weight ? d->con_weight[a * ne_stage + b] : (a == b ? 1e4 : 0.0);
-    for (int a = ne_stage; a < ne; ++a)   // e_T^T W e_T once (mpc.py:1686): a terminal weight on the constant state e_T
-      for (int b = ne_stage; b < ne; ++b)
-        c.cost[gv->o_wn + (nx + nth + a) * nxe + (nx + nth + b)] =
-            d->tcon_weight ? d->tcon_weight[(a - ne_stage) * d->n_tcon + (b - ne_stage)] : (a == b ? 1e4 : 0.0);
+    // cost block layout of NmpcGen (hilo_nmpc_gen.h): the slack penalties are weights on the engine's states e
+    pack_quad_cost(c.cost, {gv->o_wz, gv->o_zref, gv->o_wn, gv->o_xrefn, gv->o_wdu, gv->o_hasdu, nxe, nz, nxe}, d, nx, nu, nth);
+    const int ie = nx + nth;
+    pack_slack_weight(c.cost, gv->o_wz + ie * nz + ie, nz, d->con_weight, ne_stage);   // e^T W e once per stage (mpc.py:1708)
+    // e_T^T W e_T once (mpc.py:1686): a terminal weight on the constant state e_T
+    pack_slack_weight(c.cost, gv->o_wn + (ie + ne_stage) * nxe + ie + ne_stage, nxe, d->tcon_weight, ne - ne_stage);
     int rcode = HILO_OK;
     const char* why = "";
     int plen = 0;
@@ -335,7 +247,7 @@ extern "C" int hilo_nmpc_create(const hilo_nmpc_desc* d, int device, hilo_nmpc**
       rcode = fail(HILO_EINVAL, "hilo_nmpc_create: terminal constraint program: %s", why);
     if (!rcode && gv->o_prog + plen + (d->n_con > 0 ? d->con_prog_len : 0) + (d->n_tcon > 0 ? d->tcon_prog_len : 0) > OCP_NCOST)
       rcode = fail(HILO_ENOTSUP, "expression programs too long (%d doubles available)", OCP_NCOST - gv->o_prog);
-    if (rcode) { delete h; return rcode; }
+    if (rcode) return rcode;
     for (int i = 0; i < plen; ++i) c.cost[gv->o_prog + i] = d->path_prog[i];
     if (d->n_con > 0)
       for (int i = 0; i < d->con_prog_len; ++i) c.cost[gv->o_prog + plen + i] = d->con_prog[i];
@@ -345,67 +257,45 @@ extern "C" int hilo_nmpc_create(const hilo_nmpc_desc* d, int device, hilo_nmpc**
     }
     c.cost[gv->o_nexpr] = d->n_con;
     c.cost[gv->o_ntexpr] = d->n_tcon;
-    c.nc = nrow;
-    c.nc_term = ntrow;
-    c.n_con_ref = n_con_ref;
-    c.n_tcon_ref = n_tcon_ref;
+    c.nc = rows.n;
+    c.nc_term = trows.n;
+    c.n_con_ref = rows.nref;
+    c.n_tcon_ref = trows.nref;
     c.cost[gv->o_tsoft] = d->tcon_soft ? 1.0 : 0.0;
     for (int m = 0; m < OCP_MAXNC; ++m) { c.dlb[m] = -INFINITY; c.dub[m] = INFINITY; }
-    for (int m = 0; m < nrow; ++m) {
-      c.cost[gv->o_rowx + m] = row_expr[m]; c.cost[gv->o_rows + m] = row_sign[m]; c.cost[gv->o_rowe + m] = row_e[m];
-      c.dlb[m] = relaxed_lb(row_lb[m]); c.dub[m] = relaxed_ub(row_ub[m]);   // IPOPT relaxes constraint bounds alike
-      c.row_ref[m] = (short)row_ref[m];
+    for (int m = 0; m < rows.n; ++m) {
+      c.cost[gv->o_rowx + m] = rows.expr[m]; c.cost[gv->o_rows + m] = rows.sign[m]; c.cost[gv->o_rowe + m] = rows.e[m];
+      c.dlb[m] = rows.lb[m]; c.dub[m] = rows.ub[m];
+      relax_box(c.dlb[m], c.dub[m], c.bound_relax);   // IPOPT relaxes constraint bounds alike
+      c.row_ref[m] = (short)rows.ref[m];
     }
-    for (int r = 0; r < ntrow; ++r) {
-      c.cost[gv->o_trowx + r] = trow_expr[r]; c.cost[gv->o_trows + r] = trow_sign[r]; c.cost[gv->o_trowe + r] = trow_e[r];
-      c.dlb[nrow + r] = relaxed_lb(trow_lb[r]); c.dub[nrow + r] = relaxed_ub(trow_ub[r]);
-      c.trow_ref[r] = (short)trow_ref[r];
+    for (int r = 0; r < trows.n; ++r) {
+      c.cost[gv->o_trowx + r] = trows.expr[r]; c.cost[gv->o_trows + r] = trows.sign[r]; c.cost[gv->o_trowe + r] = trows.e[r];
+      c.dlb[rows.n + r] = trows.lb[r]; c.dub[rows.n + r] = trows.ub[r];
+      relax_box(c.dlb[rows.n + r], c.dub[rows.n + r], c.bound_relax);
+      c.trow_ref[r] = (short)trows.ref[r];
     }
     for (int i = nx; i < nxe; ++i) c.x0_free_mask |= 1u << i;               // theta_0 and e are variables (mpc.py:785-789)
     for (int a = 0; a < ne; ++a) c.k0_only_mask |= 1u << (nx + nth + a);    // one box on the shared slack
   }
-  for (int i = 0; i < nz; ++i) {
-    // bounds arrive in original units; scaled like mpc.py:253-259, then relaxed like IPOPT's bound_relax_factor
-    double lb = -INFINITY, ub = INFINITY;
-    if (i < nx) { if (d->x_lb) lb = d->x_lb[i] / c.sz[i]; if (d->x_ub) ub = d->x_ub[i] / c.sz[i]; }
-    else if (i < nx + nth) { lb = d->theta_lb; ub = d->theta_ub; }                                  // mpc.py:1198-1199
-    else if (i < nxe) {                                                                             // :1533-1534, :1544-1545
-      const int a = i - nx - nth;
-      lb = 0.0;
-      ub = a < ne_stage ? (d->con_max_violation ? d->con_max_violation[a] : INFINITY)
-                        : (d->tcon_max_violation ? d->tcon_max_violation[a - ne_stage] : INFINITY);
-    }
-    else if (i < nxe + nu) { const int j = i - nxe; if (d->u_lb) lb = d->u_lb[j] / c.sz[i]; if (d->u_ub) ub = d->u_ub[j] / c.sz[i]; }
-    else { lb = d->u_pf_lb; ub = d->u_pf_ub; }                                                      // mpc.py:1196-1197
-    lb = relaxed_lb(lb); ub = relaxed_ub(ub);
-    if (!(lb < ub)) { delete h; return fail(HILO_EINVAL, "hilo_nmpc_create: empty box for variable %d", i); }
-    c.lbz[i] = lb; c.ubz[i] = ub;
-  }
-  if (d->tol > 0) c.tol = d->tol;
-  if (d->acceptable_tol > 0) c.acceptable_tol = d->acceptable_tol;
-  if (d->mu_init > 0) c.mu_init = d->mu_init;
-  if (d->max_hessian_perturbation > 0) c.delta_w_max = d->max_hessian_perturbation;
+  rc = nmpc_scale_boxes(c, d, nx, nu, nth, ne_stage, ne, ne, 0);
+  if (rc) return rc;
   hipError_t e = hipSetDevice(device);
   if (d->model_id == HILO_MODEL_CHEMOSTAT4_GP) {
     // dynamic_model.py:3040-3125: the label `mu` is replaced by the posterior mean over the features (S, I)
-    if (!d->learned) {
-      hilo_nmpc_destroy(h);
+    if (!d->learned)
       return fail(HILO_EINVAL, "hilo_nmpc_create: model 'chemostat4_gp' needs desc.learned (a hilo_gp over the features S, I)");
-    }
     rc = gp_pack_se2(d->learned, &h->ext_pack);
-    if (rc) { hilo_nmpc_destroy(h); return rc; }
+    if (rc) return rc;
     {
       double nterms = 0.0;   // the solve kernel stages the table in LDS (hilo_models.h GP2_MAXN)
       HILO_HIP_CHECK(hipMemcpy(&nterms, h->ext_pack, sizeof(double), hipMemcpyDeviceToHost));
-      if (nterms > GP2_MAXN) {
-        hilo_nmpc_destroy(h);
+      if (nterms > GP2_MAXN)
         return fail(HILO_ENOTSUP, "hilo_nmpc_create: the learned term of 'chemostat4_gp' has %d training points (limit %d)", (int)nterms,
                     GP2_MAXN);
-      }
     }
     c.ext = h->ext_pack;
   } else if (d->learned) {
-    hilo_nmpc_destroy(h);
     return fail(HILO_EINVAL, "hilo_nmpc_create: desc.learned given but model %d has no learned term", d->model_id);
   }
   h->base_free_mask = c.x0_free_mask;
@@ -418,40 +308,21 @@ extern "C" int hilo_nmpc_create(const hilo_nmpc_desc* d, int device, hilo_nmpc**
     rq.sym = (d->n_sub <= 1) && !getenv("HILO_NMPC_TAYLOR");
     rq.private_module = d->n_user_gp > 0;
     rc = jit_nmpc_kernels(rq, device, &h->jit);
-    if (!rc && getenv("HILO_JIT_COMPILE_ONLY")) { hilo_nmpc_destroy(h); return HILO_COMPILED_ONLY; }   // cache warmed, no handle
+    if (!rc && getenv("HILO_JIT_COMPILE_ONLY")) return HILO_COMPILED_ONLY;   // cache warmed, no handle
     if (!rc && (h->jit.dims[0] != nx || h->jit.dims[1] != nu || h->jit.dims[2] != np))
       rc = fail(HILO_EINVAL, "hilo_nmpc_create: the compiled UserModel has (nx, nu, np) = (%d, %d, %d), the description says (%d, %d, %d)",
                 h->jit.dims[0], h->jit.dims[1], h->jit.dims[2], nx, nu, np);
-    if (!rc) rc = nmpc_bind_user_gps(h, d);
-    if (rc) { hilo_nmpc_destroy(h); return rc; }
+    if (!rc) rc = nmpc_bind_user_gps(h.get(), d);
+    if (rc) return rc;
     h->jit_policy = JIT_TRACK;
     h->lds_bytes = 0;   // static LDS inside the compiled kernel
     h->jit_ws_bytes = jit_big ? ocp_iter_doubles(nx, nu, 0, d->N) * sizeof(double) : 0;
   }
-  if (e == hipSuccess) e = hipMalloc((void**)&h->dev, sizeof(OcpConst));
-  if (e == hipSuccess) e = hipMemcpy(h->dev, &c, sizeof(OcpConst), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMalloc((void**)&h->v_guess, sizeof(double) * h->n_v);
-  if (e == hipSuccess) {
-    // mpc.py:1468-1482: the guess is tiled over the horizon (scaled, mpc.py:255,259)
-    double* g = new double[h->n_v];
-    for (int i = 0; i < h->n_v; ++i) g[i] = 0.0;   // shared slack starts at 0 (mpc.py:1535)
-    for (int k = 0; k <= d->N; ++k) {
-      for (int i = 0; i < nx; ++i) g[k * nxv + i] = (d->x_guess ? d->x_guess[i] : 0.0) / sx[i];
-      if (nth) g[k * nxv + nx] = d->theta_guess;                                              // mpc.py:1194
-    }
-    for (int k = 0; k < d->N; ++k) {
-      for (int i = 0; i < nu; ++i) g[(d->N + 1) * nxv + k * nue + i] = (d->u_guess ? d->u_guess[i] : 0.0) / su[i];
-      if (nth) g[(d->N + 1) * nxv + k * nue + nu] = d->u_pf_lb + 0.0001;                      // mpc.py:1195
-    }
-    for (int q = 0; q < d->N * dn; ++q) g[h->n_vc + q] = (d->x_guess ? d->x_guess[q % nx] : 0.0) / sx[q % nx];   // mpc.py:1321
-    e = hipMemcpy(h->v_guess, g, sizeof(double) * h->n_v, hipMemcpyHostToDevice);
-    delete[] g;
-  }
-  if (e != hipSuccess) {
-    hilo_nmpc_destroy(h);
-    return fail(HILO_EHIP, "hilo_nmpc_create: %s", hipGetErrorString(e));
-  }
-  *out = h;
+  const std::vector<double> g = nmpc_guess(d, h->n_v, c.sz, c.sz + nxe, nx, nu, nth, d->N, D, h->n_vc, dn);
+  if (e == hipSuccess) e = ocp_upload(&h->dev, &c, sizeof(OcpConst));
+  if (e == hipSuccess) e = ocp_upload(&h->v_guess, g.data(), sizeof(double) * h->n_v);
+  if (e != hipSuccess) return fail(HILO_EHIP, "hilo_nmpc_create: %s", hipGetErrorString(e));
+  *out = h.release();
   return HILO_OK;
 }
 
@@ -485,11 +356,9 @@ extern "C" int hilo_nmpc_set_x0_box(hilo_nmpc* h, const double* x0_lb_host, cons
   OcpConst& c = h->host;
   const bool on = x0_lb_host || x0_ub_host;
   if (!on && !(c.flags & 2)) return HILO_OK;
-  const double relax = 1e-8;
   for (int i = 0; i < h->nx; ++i) {
     double lb = x0_lb_host ? x0_lb_host[i] / c.sz[i] : -INFINITY, ub = x0_ub_host ? x0_ub_host[i] / c.sz[i] : INFINITY;
-    if (lb > -INFINITY) lb -= relax * fmax(1.0, fabs(lb));
-    if (ub < INFINITY) ub += relax * fmax(1.0, fabs(ub));
+    relax_box(lb, ub, 1e-8);   // IPOPT's default factor: does not follow desc.bound_relax_factor
     HILO_REQUIRE(lb < ub, "hilo_nmpc_set_x0_box: empty box for state %d", i);
     c.x0lb[i] = lb; c.x0ub[i] = ub;
   }
@@ -610,19 +479,15 @@ static int nmpc_solve_impl(hilo_nmpc* h, int64_t batch, const double* x0, const 
   const bool direct = nmpc_is_direct(h);
   if (direct) {
     if (h->warm_batch != batch) {
-      if (h->v_warm) HILO_HIP_CHECK(hipFree(h->v_warm));
-      h->v_warm = nullptr;
-      hipError_t e = hipMalloc((void**)&h->v_warm, sizeof(double) * h->n_v * batch);
-      if (e != hipSuccess) return fail(HILO_ENOMEM, "warm-start buffer: %s", hipGetErrorString(e));
+      const int rc = batch_realloc(&h->v_warm, sizeof(double) * h->n_v * batch, "warm-start buffer: %s");
+      if (rc) return rc;
       h->warm_batch = batch;
       h->warm_valid = 0;
     }
   } else {
     if (h->par_batch != batch) {
-      if (h->par_buf) HILO_HIP_CHECK(hipFree(h->par_buf));
-      h->par_buf = nullptr;
-      hipError_t e = hipMalloc((void**)&h->par_buf, sizeof(double) * (size_t)w * batch);
-      if (e != hipSuccess) return fail(HILO_ENOMEM, "parameter buffer: %s", hipGetErrorString(e));
+      const int rc = batch_realloc(&h->par_buf, sizeof(double) * (size_t)w * batch, "parameter buffer: %s");
+      if (rc) return rc;
       h->par_batch = batch;
     }
     const int64_t tot = batch * w;
@@ -659,21 +524,17 @@ static int nmpc_solve_impl(hilo_nmpc* h, int64_t batch, const double* x0, const 
   if (h->jit_policy >= 0) {
     const size_t wsb = h->jit_ws_bytes;
     if (wsb && h->ws_batch != batch) {
-      if (h->ws) HILO_HIP_CHECK(hipFree(h->ws));
-      h->ws = nullptr;
-      hipError_t e = hipMalloc((void**)&h->ws, wsb * (size_t)batch);
-      if (e != hipSuccess) return fail(HILO_ENOMEM, "iterate workspace (%zu B per instance): %s", wsb, hipGetErrorString(e));
+      rc = batch_realloc(&h->ws, wsb * (size_t)batch, "iterate workspace (%zu B per instance): %s", wsb);
+      if (rc) return rc;
       h->ws_batch = batch;
     }
     double *vout = v_opt, *lout = lam_g;
     if (h->jit_coll_d > 0) {   // the engine writes its compact solution; the output pass adds the collocation states / rows
       if (h->vc_batch != batch) {
-        if (h->vc) HILO_HIP_CHECK(hipFree(h->vc));
-        if (h->lamc) HILO_HIP_CHECK(hipFree(h->lamc));
-        h->vc = h->lamc = nullptr;
-        hipError_t e = hipMalloc((void**)&h->vc, sizeof(double) * (size_t)h->n_vc * batch);
-        if (e == hipSuccess) e = hipMalloc((void**)&h->lamc, sizeof(double) * (size_t)(h->n_gc ? h->n_gc : h->N * h->nxv) * batch);
-        if (e != hipSuccess) return fail(HILO_ENOMEM, "collocation output buffers: %s", hipGetErrorString(e));
+        rc = batch_realloc(&h->vc, sizeof(double) * (size_t)h->n_vc * batch, "collocation output buffers: %s");
+        if (!rc)
+          rc = batch_realloc(&h->lamc, sizeof(double) * (size_t)(h->n_gc ? h->n_gc : h->N * h->nxv) * batch, "collocation output buffers: %s");
+        if (rc) return rc;
         h->vc_batch = batch;
       }
       vout = h->vc; lout = h->lamc;
@@ -689,12 +550,9 @@ static int nmpc_solve_impl(hilo_nmpc* h, int64_t batch, const double* x0, const 
     rc = h->tv->launch(a, stage_data, sd_stride);
   } else if (h->coll) {
     if (h->vc_batch != batch) {
-      if (h->vc) HILO_HIP_CHECK(hipFree(h->vc));
-      if (h->lamc) HILO_HIP_CHECK(hipFree(h->lamc));
-      h->vc = h->lamc = nullptr;
-      hipError_t e = hipMalloc((void**)&h->vc, sizeof(double) * (size_t)h->n_vc * batch);
-      if (e == hipSuccess) e = hipMalloc((void**)&h->lamc, sizeof(double) * (size_t)h->N * h->nx * batch);
-      if (e != hipSuccess) return fail(HILO_ENOMEM, "collocation output buffers: %s", hipGetErrorString(e));
+      rc = batch_realloc(&h->vc, sizeof(double) * (size_t)h->n_vc * batch, "collocation output buffers: %s");
+      if (!rc) rc = batch_realloc(&h->lamc, sizeof(double) * (size_t)h->N * h->nx * batch, "collocation output buffers: %s");
+      if (rc) return rc;
       h->vc_batch = batch;
     }
     // the engine reads the [x | u] head of each (full-layout) start row and writes its compact solution
@@ -706,10 +564,8 @@ static int nmpc_solve_impl(hilo_nmpc* h, int64_t batch, const double* x0, const 
   } else if (h->gen || h->big) {
     const size_t wsb = h->gen ? h->gen->ws_bytes(h->N) : h->big->ws_bytes(h->N);
     if (wsb && h->ws_batch != batch) {
-      if (h->ws) HILO_HIP_CHECK(hipFree(h->ws));
-      h->ws = nullptr;
-      hipError_t e = hipMalloc((void**)&h->ws, wsb * (size_t)batch);
-      if (e != hipSuccess) return fail(HILO_ENOMEM, "iterate workspace (%zu B per instance): %s", wsb, hipGetErrorString(e));
+      rc = batch_realloc(&h->ws, wsb * (size_t)batch, "iterate workspace (%zu B per instance): %s", wsb);
+      if (rc) return rc;
       h->ws_batch = batch;
     }
     GenLaunchArgs a{h->dev, batch, x0, h->par_buf, (int64_t)(h->np + h->nu), vstart, vstride, v_opt, f_opt, lam_g, u0,
@@ -729,10 +585,8 @@ static int nmpc_solve_impl(hilo_nmpc* h, int64_t batch, const double* x0, const 
   if (direct) { h->warm_valid = 1; return HILO_OK; }   // the solve wrote the warm-start copy itself
   // keep the solution for the next call (un-shifted, like the reference)
   if (h->warm_batch != batch) {
-    if (h->v_warm) HILO_HIP_CHECK(hipFree(h->v_warm));
-    h->v_warm = nullptr;
-    hipError_t e = hipMalloc((void**)&h->v_warm, sizeof(double) * h->n_v * batch);
-    if (e != hipSuccess) return fail(HILO_ENOMEM, "warm-start buffer: %s", hipGetErrorString(e));
+    rc = batch_realloc(&h->v_warm, sizeof(double) * h->n_v * batch, "warm-start buffer: %s");
+    if (rc) return rc;
     h->warm_batch = batch;
   }
   HILO_HIP_CHECK(hipMemcpyAsync(h->v_warm, v_opt, sizeof(double) * h->n_v * batch, hipMemcpyDeviceToDevice, s));
