@@ -28,6 +28,11 @@ class KfDesc(C.Structure):
                 ('user_source', C.c_char_p), ('n_user_gp', C.c_int32), ('user_gp', C.c_void_p * 4)]
 
 
+class SimOpts(C.Structure):
+    """hilo_sim_opts: method 0 = the handle's own map, 1 = HILO_SIM_DOPRI5."""
+    _fields_ = [('method', C.c_int32), ('max_steps', C.c_int32), ('rtol', C.c_double), ('atol', C.c_double), ('h0', C.c_double)]
+
+
 class NmpcDesc(C.Structure):
     _fields_ = [('model_id', C.c_int32), ('N', C.c_int32), ('Nc', C.c_int32), ('erk_order', C.c_int32),
                 ('n_sub', C.c_int32), ('max_iter', C.c_int32), ('acceptable_iter', C.c_int32), ('reserved', C.c_int32),
@@ -93,6 +98,7 @@ def _declare(lib):
         'hilo_kf_update': (C.c_int, [vp, i64, vp, vp, vp, i64, vp, i64, vp, vp, vp]),
         'hilo_kf_step': (C.c_int, [vp, i64, vp, vp, vp, i64, vp, i64, vp, i64, vp, vp, vp]),
         'hilo_pf_function': (C.c_int, [vp, i64, i32, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, vp]),
+        'hilo_model_rollout': (C.c_int, [vp, P(SimOpts), i64, i32, vp, vp, i64, i64, vp, vp, vp, vp]),
         'hilo_pf_stats': (C.c_int, [vp, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         'hilo_pf_resample': (C.c_int, [vp, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
         'hilo_nmpc_create': (C.c_int, [P(NmpcDesc), i32, P(vp)]),

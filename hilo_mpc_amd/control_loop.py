@@ -5,7 +5,8 @@ What the reference's `_run` does per iteration (control_loop.py:343-397): `u = c
 controller's model], cp=p)`, `plant.simulate(u=u, p=p)`, `observer.estimate()` - the controller is fed the PLANT state, the
 observer runs alongside.  Here the plant is advanced on the device: with the controller's shooting map when it is the
 controller's own model (`NMPC.plant_step`), with `Model.step` for a plant model of its own (a continuous plant is integrated with
-eight classic Runge-Kutta steps per interval in place of the reference's CVODES), or by a callable `(x, u, p) -> x+`."""
+eight classic Runge-Kutta steps per interval, or - set up with `Model.setup(solver='dopri5')` - under error control like the
+reference's CVODES), or by a callable `(x, u, p) -> x+`."""
 import numpy as np
 import torch
 

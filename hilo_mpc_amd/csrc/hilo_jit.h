@@ -57,6 +57,8 @@ struct JitKfKernels {
   hipFunction_t pf = nullptr;   // particle-filter function of the same model (hilo_kf_kernel.h::pf_body)
   hipFunction_t multi[2] = {nullptr, nullptr};   // several fused steps per launch (kf_multi_body): [UKF]
   hipFunction_t team[2] = {nullptr, nullptr};    // the same on a team of lanes per instance (kf_team_body): small batches
+  hipFunction_t rollout = nullptr;               // many sampling intervals per launch (hilo_integrate.h::rollout_body)
+  int rollout_scratch = 0;                       // bytes of scratch per lane of that kernel (0: everything in registers)
   int dims[5] = {0, 0, 0, 0, 0};
   const double** gp_table = nullptr;   // device address of the module's hilo_user_gp[4] (learned terms of the user model)
   hipModule_t owned = nullptr;         // a module instance of the filter's own (private_module): unloaded with the handle

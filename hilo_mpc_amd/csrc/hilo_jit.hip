@@ -355,11 +355,12 @@ int jit_nmpc_kernels(const JitRequest& r, int device, JitKernels* out) {
   return HILO_OK;
 }
 
-// ---- filters of models written as expressions: kf_body<UserModel, UKF, MODE> behind six extern "C" kernels ----------------
+// ---- filters of models written as expressions: kf_body<UserModel, UKF, MODE> behind six extern "C" kernels, the fused / team /
+// particle variants and the roll-out (csrc/hilo_integrate.h::rollout_body) -------------------------------------------------
 static std::map<std::string, JitKfKernels> g_kf_loaded;
 
 int jit_kf_kernels(const std::string& user_source, int device, JitKfKernels* out, bool compile_only, bool private_module) {
-  std::string tu = "#include \"hilo_kf_kernel.h\"\nextern \"C\" { __device__ const double* hilo_user_gp[4]; }\nnamespace hilo {\n";
+  std::string tu = "#include \"hilo_kf_kernel.h\"\n#include \"hilo_integrate.h\"\nextern \"C\" { __device__ const double* hilo_user_gp[4]; }\nnamespace hilo {\n";
   tu += user_source;
   tu += R"(
 }  // namespace hilo
@@ -416,6 +417,13 @@ extern "C" __global__ __launch_bounds__(PF_TPB) void hilo_user_pf(KfParams kp, i
   pf_body<UserModel>(kp, n, X + b * n * NX, y + b * NYE, up + b * up_stride, w + b * n * NX, v + b * n * NYE, R + b * r_stride,
                      Xp + b * n * NX, Y + b * n * NYE, q + b * n);
 }
+extern "C" __global__ __launch_bounds__(ROLLOUT_TPB) void hilo_user_rollout(KfParams kp, SimParams sp, int64_t batch, int steps,
+                                                                            const double* __restrict__ x0,
+                                                                            const double* __restrict__ up, int64_t up_stride,
+                                                                            int64_t up_step, double* __restrict__ X,
+                                                                            double* __restrict__ Y, int* __restrict__ stats) {
+  rollout_body<UserModel>(kp, sp, batch, steps, x0, up, up_stride, up_step, X, Y, stats);
+}
 extern "C" __global__ void hilo_user_kf_info(int* o) {
   o[0] = UserModel::NX; o[1] = UserModel::NU; o[2] = UserModel::NP; o[3] = UserModel::NY; o[4] = UserModel::DISCRETE ? 1 : 0;
 }
@@ -448,6 +456,8 @@ extern "C" __global__ void hilo_user_kf_info(int* o) {
   HILO_HIP_CHECK(hipModuleGetFunction(&k.multi[1], mod, "hilo_user_kf_um"));
   HILO_HIP_CHECK(hipModuleGetFunction(&k.team[0], mod, "hilo_user_kf_et"));
   HILO_HIP_CHECK(hipModuleGetFunction(&k.team[1], mod, "hilo_user_kf_ut"));
+  HILO_HIP_CHECK(hipModuleGetFunction(&k.rollout, mod, "hilo_user_rollout"));
+  if (hipFuncGetAttribute(&k.rollout_scratch, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, k.rollout) != hipSuccess) k.rollout_scratch = 0;
   hipFunction_t info = nullptr;
   HILO_HIP_CHECK(hipModuleGetFunction(&info, mod, "hilo_user_kf_info"));
   int* dinfo = nullptr;

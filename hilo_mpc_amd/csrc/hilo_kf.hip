@@ -2,7 +2,7 @@
 //
 // Reference semantics: hilo_mpc/modules/estimator/kf.py
 //   predict  :71-133   (UKF :505-554)      update :135-186 (UKF :556-604)      step = update(predict) :258-265
-#include "hilo_jit.h"
+#include "hilo_kf_handle.h"
 #include "hilo_kf_kernel.h"
 
 namespace hilo {
@@ -103,23 +103,6 @@ int launch_multi(const KfParams& kp, int64_t batch, int steps, const double* in,
 }  // namespace hilo
 
 using namespace hilo;
-
-struct hilo_kf {
-  hilo_kf_desc desc;
-  int device;
-  int nx, nu, np, ny;
-  bool discrete;
-  KfParams kp;
-  hilo::JitKfKernels jit;   // model given as source (HILO_MODEL_USER): kernels compiled at create
-  double* user_gp_pack[4] = {nullptr, nullptr, nullptr, nullptr};   // packed learned terms of that model (gp_pack_se)
-};
-
-#define HILO_KF_MODELS(X)                 \
-  X(HILO_MODEL_TOY1D, Toy1D)              \
-  X(HILO_MODEL_BIOREACTOR3, Bioreactor3)  \
-  X(HILO_MODEL_CHEMOSTAT4, Chemostat4)    \
-  X(HILO_MODEL_PENDULUM4, Pendulum4)      \
-  X(HILO_MODEL_LINEAR2, Linear2)
 
 static int kf_model_dims(const hilo_kf_desc* d, int* nx, int* nu, int* np, int* ny, int* discrete) {
   switch (d->model_id) {

@@ -8,20 +8,12 @@
 // picked up row-per-lane (hilo_common.h), all arithmetic is register-resident fp64 with compile-time shapes.
 #pragma once
 #include "hilo_common.h"
+#include "hilo_kf_params.h"
 #include "hilo_models.h"
 
 namespace hilo {
 
 constexpr int KF_TPB = 64;   // one wave per workgroup
-
-struct KfParams {
-  int kind, continuous, erk_order, n_sub;
-  double dt, gamma, wm0, wc0, wi;  // UKF: W_m[0], W_c[0], W[1:] (kf.py:493-500)
-  // hilo_kf_steps_split: the parameters in their own array (rows of np doubles, stride pp_stride or 0 = shared) - `up` then holds
-  // the inputs alone (rows of nu doubles); nullptr: `up` holds the packed rows [u; p]
-  const double* pp = nullptr;
-  long long pp_stride = 0;
-};
 
 template <int N> struct MaxOne { static constexpr int v = N > 0 ? N : 1; };
 

@@ -1,0 +1,99 @@
+// Batched roll-out of a handle's model over many sampling intervals in one launch: C ABI and launches (device code:
+// csrc/hilo_integrate.h).
+//
+// Reference semantics: `Model.simulate` (hilo_mpc/modules/dynamic_model/dynamic_model.py:3911-4000) - inputs held over a
+// sampling interval, the state and the measurements recorded at every sampling instant - for a batch of instances.
+#include "hilo_integrate.h"
+#include "hilo_kf_handle.h"
+
+namespace hilo {
+
+template <class M, int METHOD>
+__global__ __launch_bounds__(ROLLOUT_TPB) void rollout_kernel(KfParams kp, SimParams sp, int64_t batch, int steps,
+                                                              const double* __restrict__ x0, const double* __restrict__ up,
+                                                              int64_t up_stride, int64_t up_step, double* __restrict__ X,
+                                                              double* __restrict__ Y, int* __restrict__ stats) {
+  rollout_body<M, METHOD>(kp, sp, batch, steps, x0, up, up_stride, up_step, X, Y, stats);
+}
+
+template <class M>
+static int rollout_launch(const KfParams& kp, const SimParams& sp, int64_t batch, int steps, const double* x0, const double* up,
+                          int64_t us, int64_t ustep, double* X, double* Y, int* stats, hipStream_t s) {
+  const unsigned grid = (unsigned)((batch + ROLLOUT_TPB - 1) / ROLLOUT_TPB);
+  if (sp.method == SIM_DOPRI5) {
+    if constexpr (!M::DISCRETE)
+      hipLaunchKernelGGL((rollout_kernel<M, SIM_DOPRI5>), dim3(grid), dim3(ROLLOUT_TPB), 0, s, kp, sp, batch, steps, x0, up, us, ustep, X,
+                         Y, stats);
+    else
+      return fail(HILO_ENOTSUP, "hilo_model_rollout: HILO_SIM_DOPRI5 on a discrete model");
+  } else {
+    hipLaunchKernelGGL((rollout_kernel<M, SIM_MAP>), dim3(grid), dim3(ROLLOUT_TPB), 0, s, kp, sp, batch, steps, x0, up, us, ustep, X, Y,
+                       stats);
+  }
+  HILO_HIP_CHECK(hipGetLastError());
+  return HILO_OK;
+}
+
+}  // namespace hilo
+
+using namespace hilo;
+
+static_assert(HILO_SIM_DOPRI5_MAX_NX == DOPRI5_MAX_NX && HILO_SIM_DOPRI5 == SIM_DOPRI5 && HILO_SIM_STATUS_MAX_STEPS == SIM_MAX_STEPS &&
+              HILO_SIM_STATUS_STEP_TOO_SMALL == SIM_STEP_TOO_SMALL, "include/hilo_hip.h and csrc/hilo_integrate.h disagree");
+
+extern "C" int hilo_model_rollout(hilo_kf* kf, const hilo_sim_opts* opts, int64_t batch, int steps, const double* x0,
+                                  const double* up, int64_t up_stride, int64_t up_step, double* X, double* Y, int32_t* stats,
+                                  void* stream) {
+  HILO_REQUIRE(kf, "hilo_model_rollout: NULL handle");
+  HILO_REQUIRE(batch >= 0 && steps >= 1, "hilo_model_rollout: need batch >= 0 and steps >= 1");
+  SimParams sp = {SIM_MAP, 10000, 1e-6, 1e-8, 0.0};
+  if (opts) {
+    HILO_REQUIRE(opts->method == HILO_SIM_MAP || opts->method == HILO_SIM_DOPRI5, "hilo_model_rollout: unknown method %d", opts->method);
+    sp.method = opts->method;
+    if (opts->max_steps > 0) sp.max_steps = opts->max_steps;
+    if (opts->rtol > 0.0) sp.rtol = opts->rtol;
+    if (opts->atol > 0.0) sp.atol = opts->atol;
+    if (opts->h0 > 0.0) sp.h0 = opts->h0;
+  }
+  if (sp.method == SIM_DOPRI5) {
+    if (kf->discrete || !kf->kp.continuous)
+      return fail(HILO_ENOTSUP, "hilo_model_rollout: HILO_SIM_DOPRI5 integrates a continuous model; this handle holds a discrete "
+                                "(or discretised) one");
+    if (kf->nx > HILO_SIM_DOPRI5_MAX_NX)
+      return fail(HILO_ENOTSUP, "hilo_model_rollout: HILO_SIM_DOPRI5 keeps its slopes in registers and is built for up to %d states; "
+                                "the model has %d", HILO_SIM_DOPRI5_MAX_NX, kf->nx);
+    if (kf->desc.model_id == 100 /* HILO_MODEL_USER */ && kf->jit.rollout_scratch > 0)
+      return fail(HILO_ENOTSUP, "hilo_model_rollout: the compiled right-hand side of this model leaves HILO_SIM_DOPRI5 %d bytes of scratch "
+                                "memory per lane; the pair is built to keep its slopes in registers", kf->jit.rollout_scratch);
+  }
+  if (batch == 0) return HILO_OK;
+  HILO_REQUIRE(x0 && X, "hilo_model_rollout: NULL argument");
+  HILO_REQUIRE(kf->nu + kf->np == 0 || up, "hilo_model_rollout: the model has %d inputs/parameters but `up` is NULL", kf->nu + kf->np);
+  HILO_REQUIRE(up_stride == 0 || up_stride >= kf->nu + kf->np, "hilo_model_rollout: up_stride %lld < nu+np", (long long)up_stride);
+  HILO_REQUIRE(up_step == 0 || up_step >= (up_stride ? batch * up_stride : kf->nu + kf->np),
+               "hilo_model_rollout: up_step %lld is shorter than one sampling interval's rows", (long long)up_step);
+  HILO_HIP_CHECK(hipSetDevice(kf->device));
+  hipStream_t s = (hipStream_t)stream;
+  const KfParams& kp = kf->kp;
+  static const double zero = 0.0;
+  if (!up) up = &zero;   // never read (nu + np == 0); keeps the pointer arithmetic of the kernel defined
+  int* st = (int*)stats;
+  if (kf->desc.model_id == 100 /* HILO_MODEL_USER */) {
+    HILO_REQUIRE(kf->jit.rollout, "hilo_model_rollout: the run-time compiled roll-out kernel is not loaded");
+    KfParams kpv = kp;
+    void* args[] = {&kpv, &sp, &batch, &steps, &x0, &up, &up_stride, &up_step, &X, &Y, &st};
+    const unsigned grid = (unsigned)((batch + ROLLOUT_TPB - 1) / ROLLOUT_TPB);
+    HILO_HIP_CHECK(hipModuleLaunchKernel(kf->jit.rollout, grid, 1, 1, ROLLOUT_TPB, 1, 1, 0, s, args, nullptr));
+    return HILO_OK;
+  }
+  switch (kf->desc.model_id) {
+#define X_(ID, T) case ID: return rollout_launch<T>(kp, sp, batch, steps, x0, up, up_stride, up_step, X, Y, st, s);
+    HILO_KF_MODELS(X_)
+#undef X_
+    case HILO_MODEL_LTI:
+      if (kf->nx == 2 && kf->ny == 1) return rollout_launch<Lti<2, 1, 1>>(kp, sp, batch, steps, x0, up, up_stride, up_step, X, Y, st, s);
+      if (kf->nx == 2 && kf->ny == 2) return rollout_launch<Lti<2, 1, 2>>(kp, sp, batch, steps, x0, up, up_stride, up_step, X, Y, st, s);
+      return rollout_launch<Lti<4, 2, 2>>(kp, sp, batch, steps, x0, up, up_stride, up_step, X, Y, st, s);
+  }
+  return fail(HILO_EINVAL, "unknown model id %d", kf->desc.model_id);
+}

@@ -35,6 +35,11 @@ NATIVE_DISCRETE = {'toy1d', 'lti'}
 ZOO_FUNCTOR = {'toy1d': 'Toy1D', 'bioreactor3': 'Bioreactor3', 'chemostat4': 'Chemostat4', 'pendulum4': 'Pendulum4',
                'robot6': 'Robot6', 'linear2': 'Linear2', 'cstr3': 'Cstr3'}
 MODEL_USER = 100    # HILO_MODEL_USER: the model is defined by expressions and compiled at setup (csrc/hilo_jit.hip)
+# `Model.setup(solver=...)`: integrators with error control and their options under CasADi's names (what the reference's
+# `solver_options` carries to `ca.integrator`), with CasADi's defaults for CVODES
+SOLVERS = {'dopri5': 1}            # name -> hilo_sim_opts.method (HILO_SIM_DOPRI5)
+SOLVER_OPTIONS = {'reltol': 1e-6, 'abstol': 1e-8, 'max_num_steps': 10000, 'first_step': 0.}
+SIM_STATUS = {0: 'ok', 1: 'max_num_steps reached', 2: 'step size too small'}     # HILO_SIM_STATUS_*
 
 
 class Model:
@@ -52,6 +57,9 @@ class Model:
 
     For `Model('lti', A=..., B=..., C=...)` the matrices define a discrete LTI system
     (`x+ = A x + B u`, `y = C x`, cf. tests/test_LMPC.py:8-19)."""
+
+    _solver = None              # `setup(solver=...)`: None = the fixed-step maps, 'dopri5' = integration with error control
+    _solver_options = None
 
     def __init__(self, name=None, A=None, B=None, C=None, discrete=None, id=None, plot_backend=None, **kwargs):
         if name == 'chemostat4_gp':
@@ -427,11 +435,42 @@ class Model:
         if not m._native_discrete:
             m.erk_order = order
             m.n_sub = n_sub
+            m._solver = m._solver_options = None      # a map needs no integrator
         return m
 
-    def setup(self, dt=None):
+    def setup(self, dt=None, solver=None, solver_options=None):
+        """dynamic_model.py `setup`: fixes the sampling interval (default 1).
+
+        solver: None keeps the fixed-step maps (a continuous model that was not discretised is simulated with eight classic
+        Runge-Kutta steps per interval, no error control).  'dopri5' integrates a continuous model with the Dormand-Prince 5(4)
+        pair under step-size control (csrc/hilo_integrate.h) wherever the model is simulated - `step`, `rollout`, `simulate`, the
+        plant of a `SimpleControlLoop` - where the reference integrates with CVODES.
+        solver_options, under CasADi's names (defaults: CasADi's for CVODES): reltol 1e-6, abstol 1e-8, max_num_steps 10000
+        (attempted steps per sampling interval), first_step 0 (estimated)."""
         if self._symbolic and self._ode is None:
             raise RuntimeError("Model is not set up: no dynamical equations (set_dynamical_equations)")
+        if solver is None and solver_options is not None:
+            raise ValueError("solver_options without a solver")
+        if solver is not None:
+            # dynamic_model.py `check_solver` (:1958-1993); what the reference warns about and then fails on is an error here
+            if not isinstance(solver, str):
+                raise TypeError("Solver type must be a string")
+            if self.discrete:
+                raise RuntimeError("Model is discrete. No solver is required.")
+            if solver not in SOLVERS:
+                raise ValueError(f"Solver '{solver}' is not available on your system. Use {' or '.join(repr(q) for q in SOLVERS)} instead")
+            if getattr(self, 'n_z', 0):
+                raise RuntimeError(f"Solver '{solver}' is not suitable for DAE systems. Use 'idas' or 'collocation' instead")
+            opts = dict(SOLVER_OPTIONS)
+            for k, v in (solver_options or {}).items():
+                if k not in SOLVER_OPTIONS:
+                    raise ValueError(f"Unknown option '{k}' for solver '{solver}'. Available options: {sorted(SOLVER_OPTIONS)}")
+                opts[k] = type(SOLVER_OPTIONS[k])(v)
+            if not (opts['reltol'] > 0. and opts['abstol'] > 0.):
+                raise ValueError("reltol and abstol must be positive")
+            if opts['max_num_steps'] < 1 or opts['first_step'] < 0.:
+                raise ValueError("max_num_steps must be at least 1 and first_step non-negative")
+            self._solver, self._solver_options = solver, opts
         if dt is not None:
             self.dt = float(dt)
         if self.dt is None:
@@ -539,6 +578,7 @@ class Model:
     def copy(self, setup=True):
         m = copy.copy(self)
         m._sim = None              # the copy simulates its own trajectory
+        m._rollout_up = None       # ... with its own buffer for the packed inputs and parameters
         if hasattr(self, '_gps'):
             m._gps = list(self._gps)    # learned terms substituted into the copy later must not appear in the original
         if getattr(self, '_gp_helpers', None):
@@ -550,7 +590,8 @@ class Model:
         """A filter handle of the library carries exactly what a plant step needs - the model functor (zoo, or compiled from the
         expressions), the sampling interval and the discretisation - and `hilo_pf_function` with one particle per instance and
         zero noise IS that step: x+ = Phi(x, u, p), y = h(x+, u, p) (a continuous model is integrated with eight classic
-        Runge-Kutta steps per interval in place of the reference's CVODES)."""
+        Runge-Kutta steps per interval and no error control; `setup(solver='dopri5')` integrates it with step-size control like the
+        reference's CVODES, through `hilo_model_rollout` on the same handle)."""
         h = getattr(self, '_plant', None)
         if h is None or h._model_stamp != (self.dt, self.erk_order, self.n_sub, id(self._ode) if self._symbolic else None):
             from .estimator import ExtendedKalmanFilter
@@ -570,6 +611,9 @@ class Model:
         from ._device import ptr, stream_ptr, to_dev
         if not self._is_setup:
             raise RuntimeError("Model is not set up. Run Model.setup() before running simulations.")
+        if self._solver is not None:          # one sampling interval under error control
+            xs, ys = self.rollout(x, u, p, steps=1, device_index=device_index)
+            return xs[1], ys[0]
         h = self._plant_handle(device_index)
         dev = h._dev
         host = not isinstance(x, torch.Tensor)
@@ -596,6 +640,74 @@ class Model:
         xn, y = xn[:, 0], y[:, 0]
         return (xn.cpu().numpy(), y.cpu().numpy()) if host else (xn, y)
 
+    def rollout(self, x0, u=None, p=None, steps=1, return_stats=False, device_index=None):
+        """The many-interval sibling of `step`: `steps` sampling intervals for a batch of states in ONE launch
+        (`hilo_model_rollout`), with the model's own map or, after `setup(solver='dopri5')`, under error control.
+
+        x0 [B, n_x]; u [B, n_u] held over the roll-out or [steps, B, n_u] one row per sampling interval, p likewise; a batch axis
+        of 1 is shared by the batch.  Returns x [steps + 1, B, n_x] (x[0] = x0) and y [steps, B, n_y] with y[k] = h(x[k + 1], u[k], p)
+        - device tensors for device tensors (no host copy), numpy for numpy - and with return_stats a dict of per-instance arrays
+        'status' (0 ok, 1 max_num_steps reached, 2 step size too small), 'n_accepted', 'n_rejected', 'n_rhs'.  The rows of an instance
+        whose integration failed are NaN from the sampling instant it did not reach.  Allocates its outputs; inputs AND
+        parameters together are packed into one buffer that is kept for the next call - calls on one model must therefore be
+        ordered on one stream (the current stream of the device at the time of the call): a second call rewrites the buffer."""
+        import ctypes
+        import torch
+        from . import _lib
+        from ._device import ptr, stream_ptr, to_dev
+        if not self._is_setup:
+            raise RuntimeError("Model is not set up. Run Model.setup() before running simulations.")
+        steps = int(steps)
+        if steps < 1:
+            raise ValueError(f"steps must be at least 1, got {steps}")
+        h = self._plant_handle(device_index)
+        dev = h._dev
+        host = not isinstance(x0, torch.Tensor)
+        xt = to_dev(x0, dev).reshape(-1, self.n_x).contiguous()
+        B = xt.shape[0]
+        parts = []
+        for v, n, what in ((u, self.n_u, 'inputs'), (self.lti_parameters() if self.name == 'lti' else p, h._n_p, 'parameters')):
+            if n:
+                if v is None:
+                    raise RuntimeError(f"The model has {n} {what}; pass them to step() / simulate().")
+                t = to_dev(v, dev)
+                if t.dim() > 3 or (t.dim() == 3 and t.shape[-1] != n):
+                    raise ValueError(f"{what}: expected [B, {n}] or [steps, B, {n}], got {list(t.shape)}")
+                t = t.reshape(1, -1, n) if t.dim() < 3 else t
+                if t.shape[0] not in (1, steps):
+                    raise ValueError(f"{what}: a sequence of {t.shape[0]} rows for {steps} sampling intervals")
+                if t.shape[1] not in (1, B):
+                    raise ValueError(f"{what}: batch {t.shape[1]} does not match {B} states")
+                parts.append(t)
+        if len(parts) == 2:
+            S, Bb = max(q.shape[0] for q in parts), max(q.shape[1] for q in parts)
+            up = getattr(self, '_rollout_up', None)
+            if up is None or up.shape != (S, Bb, self.n_u + h._n_p) or up.device != xt.device:
+                up = self._rollout_up = torch.empty(S, Bb, self.n_u + h._n_p, dtype=torch.float64, device=dev)
+            up[:, :, :self.n_u] = parts[0]
+            up[:, :, self.n_u:] = parts[1]
+        else:
+            up = parts[0].contiguous() if parts else None
+        nup = up.shape[2] if up is not None else 0
+        up_stride = nup if up is not None and up.shape[1] == B else 0
+        up_step = up.shape[1] * nup if up is not None and up.shape[0] > 1 else 0
+        ny = h._n_y
+        X = torch.empty(steps + 1, B, self.n_x, dtype=torch.float64, device=dev)
+        Y = torch.empty(steps, B, ny, dtype=torch.float64, device=dev)
+        stats = torch.empty(B, 4, dtype=torch.int32, device=dev) if return_stats else None
+        opts = _lib.SimOpts()
+        if self._solver is not None:
+            o = self._solver_options
+            opts.method, opts.max_steps = SOLVERS[self._solver], o['max_num_steps']
+            opts.rtol, opts.atol, opts.h0 = o['reltol'], o['abstol'], o['first_step']
+        _lib.check(_lib.lib().hilo_model_rollout(h._handle, ctypes.byref(opts), B, steps, ptr(xt), ptr(up), up_stride, up_step, ptr(X),
+                                                 ptr(Y), ptr(stats), stream_ptr(dev)))
+        out = (X.cpu().numpy(), Y.cpu().numpy()) if host else (X, Y)
+        if return_stats:
+            st = stats.cpu().numpy() if host else stats
+            out += ({'status': st[:, 0], 'n_accepted': st[:, 1], 'n_rejected': st[:, 2], 'n_rhs': st[:, 3]},)
+        return out
+
     def set_initial_conditions(self, x0, t0=0., z0=None):
         """dynamic_model.py:3360-3400 (a batch of states is allowed: [B, n_x])."""
         if not self._is_setup:
@@ -606,15 +718,40 @@ class Model:
         if x.shape[1] != self.n_x:
             raise ValueError(f"Dimension mismatch. Supplied dimension for the initial states is {x.shape[1]}, but required "
                              f"dimension is {self.n_x}.")
-        self._sim = {'t': [float(t0)], 'x': [x], 'y': [], 'u': []}
+        self._sim = {'t': [float(t0)], 'x': [x], 'y': [], 'u': [], 'status': [], 'n_accepted': [], 'n_rejected': []}
 
-    def simulate(self, u=None, p=None, steps=1, **kwargs):
-        """dynamic_model.py:3911-4000: advance the stored state by `steps` sampling intervals with the inputs held; results in
-        `model.solution` (`solution['x:f']` the last state, `solution['x']` the trajectory)."""
+    def simulate(self, u=None, p=None, steps=1, tf=None, **kwargs):
+        """dynamic_model.py:3911-4000: advance the stored state by `steps` sampling intervals (or up to `tf`: int(tf / dt) of them,
+        :3937-3941 - truncated, so a `tf` that floating-point division leaves just below a multiple of dt loses an interval, and tf < dt
+        does nothing) with the inputs held; results in `model.solution` (`solution['x:f']` the last state, `solution['x']` the
+        trajectory).  Without a solver and with inputs / parameters of at most two dimensions this is a loop over `step`.  With
+        `setup(solver=...)`, or with a sequence u [steps, B, n_u] (p likewise; `steps` is then taken from it), it is ONE `rollout`;
+        `solution['status']`, `['n_accepted']`, `['n_rejected']` hold the integrator's per-instance status and step counts of each
+        call."""
         if not self._is_setup:
             raise RuntimeError("Model is not set up. Run Model.setup() before running simulations.")
         if getattr(self, '_sim', None) is None:
             raise RuntimeError("No initial dynamical states found. Please set initial conditions before simulating the model.")
+        if tf is not None:
+            steps = int(tf / self.dt)             # truncated like the reference's: tf = .3 at dt = .1 is 2 intervals
+        if int(steps) == 0 and not [v for v in (u, p) if v is not None and getattr(v, 'ndim', np.ndim(v)) == 3]:
+            return                                # (tf < dt: nothing to do, on either path)
+        seq = [v for v in (u, p) if v is not None and getattr(v, 'ndim', np.ndim(v)) == 3]
+        if self._solver is not None or seq:
+            for v in seq:
+                steps = int(v.shape[0] if hasattr(v, 'shape') else len(v))
+            host = lambda v: None if v is None else np.asarray(v.cpu() if hasattr(v, 'cpu') else v, dtype=float)
+            u, p = host(u), host(p)
+            if u is not None and u.ndim < 3:
+                u = u.reshape(1, -1) if u.size == self.n_u else (u.T if u.ndim == 2 and u.shape[0] == self.n_u and u.shape[1] != self.n_u else u)
+            x, y, st = self.rollout(self._sim['x'][-1], u, p, steps=steps, return_stats=True)
+            for k in range(int(steps)):
+                self._sim['x'].append(x[k + 1]), self._sim['y'].append(y[k])
+                self._sim['u'].append(u if u is None or u.ndim < 3 else u[k])
+                self._sim['t'].append(self._sim['t'][-1] + self.dt)
+            for key in ('status', 'n_accepted', 'n_rejected'):
+                self._sim.setdefault(key, []).append(st[key])
+            return
         if u is not None:
             u = np.asarray(u.cpu() if hasattr(u, 'cpu') else u, dtype=float)
             u = u.reshape(1, -1) if u.size == self.n_u else (u.T if u.ndim == 2 and u.shape[0] == self.n_u and u.shape[1] != self.n_u else u)

@@ -169,6 +169,37 @@ int hilo_kf_steps_split(hilo_kf* kf, int64_t batch, int steps, const double* xP,
                         const double* Q, int64_t q_stride, const double* R, int64_t r_stride, double* xP_out, int keep_all,
                         double* y_pred, void* stream);
 
+/* Roll-out: `steps` sampling intervals of `batch` instances of the handle's model in ONE launch - the plant simulation of
+   `Model.simulate` (hilo_mpc/modules/dynamic_model/dynamic_model.py:3911-4000) for batches (the `kind` of the handle is
+   irrelevant).  opts NULL or method 0: the handle's own map x+ = Phi(x, u, p) - a discrete model, or the explicit Runge-Kutta
+   recipe of `discretize` (the arithmetic of hilo_pf_function without noise).  method HILO_SIM_DOPRI5: a continuous model
+   integrated with the Dormand-Prince 5(4) pair under step-size control (csrc/hilo_integrate.h: error norm and controller of
+   scipy's RK45), where the reference integrates with CVODES; inputs are held over a sampling interval, the step size is carried
+   across sampling instants, and every sampling instant is hit exactly.  HILO_ENOTSUP for method 1 on a discrete handle, and for a
+   model of more than HILO_SIM_DOPRI5_MAX_NX states or a run-time compiled one whose kernel needs scratch memory (the pair keeps its
+   slopes in registers).
+     x0 [B][nx];  up rows [u; p] like hilo_kf_steps: up_stride between instances (0: shared), up_step between sampling intervals
+     (0: held over the roll-out, else [steps][B][nu+np]);  X [steps+1][B][nx] (row 0 is x0);  Y [steps][B][ny] = h(x_{k+1}, u_k, p)
+     or NULL;  stats [B][4] int32 (status, accepted steps, rejected steps, right-hand-side evaluations) or NULL.
+   An instance whose integration fails - more than max_steps attempted steps within ONE sampling interval
+   (HILO_SIM_STATUS_MAX_STEPS), or a step below 16 eps |t| (HILO_SIM_STATUS_STEP_TOO_SMALL) - ends with that status, and its rows
+   from the sampling instant it did not reach onwards are NaN; the other instances are not affected and the call returns HILO_OK. */
+#define HILO_SIM_MAP 0
+#define HILO_SIM_DOPRI5 1
+#define HILO_SIM_DOPRI5_MAX_NX 12
+#define HILO_SIM_STATUS_OK 0
+#define HILO_SIM_STATUS_MAX_STEPS 1
+#define HILO_SIM_STATUS_STEP_TOO_SMALL 2
+typedef struct hilo_sim_opts {
+  int32_t method;     /* HILO_SIM_* */
+  int32_t max_steps;  /* attempted steps per sampling interval (<= 0: 10000) */
+  double rtol, atol;  /* <= 0: 1e-6, 1e-8 */
+  double h0;          /* first step (<= 0: estimated) */
+} hilo_sim_opts;
+int hilo_model_rollout(hilo_kf* kf, const hilo_sim_opts* opts, int64_t batch, int steps, const double* x0,
+                       const double* up, int64_t up_stride, int64_t up_step, double* X, double* Y, int32_t* stats,
+                       void* stream);
+
 /* ------------------------------------------------------------------------------------------------------- */
 /* Gaussian process: exact inference + prediction                                                           */
 /* replaces `ca.Function('prediction',[X,w,p],[mean,var])` (hilo_mpc/modules/machine_learning/gp/gp.py:      */
