@@ -31,7 +31,9 @@ from .mhe import MovingHorizonEstimator, MHE
 from .lmpc import LMPC
 from .control_loop import SimpleControlLoop
 from .pf import ParticleFilter
+from .lqr import LinearQuadraticRegulator, LQR
 
 PF = ParticleFilter
 
-__all__ += ['NMPC', 'SMPC', 'MovingHorizonEstimator', 'MHE', 'LMPC', 'expr', 'SimpleControlLoop', 'ParticleFilter', 'PF']
+__all__ += ['NMPC', 'SMPC', 'MovingHorizonEstimator', 'MHE', 'LMPC', 'expr', 'SimpleControlLoop', 'ParticleFilter', 'PF',
+            'LinearQuadraticRegulator', 'LQR']

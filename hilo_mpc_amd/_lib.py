@@ -33,6 +33,11 @@ class SimOpts(C.Structure):
     _fields_ = [('method', C.c_int32), ('max_steps', C.c_int32), ('rtol', C.c_double), ('atol', C.c_double), ('h0', C.c_double)]
 
 
+class LqrOpts(C.Structure):
+    """hilo_lqr_opts: horizon 0 = stationary."""
+    _fields_ = [('horizon', C.c_int32), ('max_iter', C.c_int32), ('tol', C.c_double)]
+
+
 class NmpcDesc(C.Structure):
     _fields_ = [('model_id', C.c_int32), ('N', C.c_int32), ('Nc', C.c_int32), ('erk_order', C.c_int32),
                 ('n_sub', C.c_int32), ('max_iter', C.c_int32), ('acceptable_iter', C.c_int32), ('reserved', C.c_int32),
@@ -99,6 +104,10 @@ def _declare(lib):
         'hilo_kf_step': (C.c_int, [vp, i64, vp, vp, vp, i64, vp, i64, vp, i64, vp, vp, vp]),
         'hilo_pf_function': (C.c_int, [vp, i64, i32, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, vp]),
         'hilo_model_rollout': (C.c_int, [vp, P(SimOpts), i64, i32, vp, vp, i64, i64, vp, vp, vp, vp]),
+        'hilo_model_linearize': (C.c_int, [vp, i64, vp, vp, i64, vp, vp, vp, vp]),
+        'hilo_lqr_gain': (C.c_int, [i32, i32, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, P(LqrOpts), vp, vp, vp, vp]),
+        'hilo_lqr_call': (C.c_int, [vp, P(LqrOpts), i64, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]),
+        'hilo_lqr_apply': (C.c_int, [i32, i32, i64, vp, i64, vp, vp, vp, vp, vp]),
         'hilo_pf_stats': (C.c_int, [vp, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         'hilo_pf_resample': (C.c_int, [vp, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
         'hilo_nmpc_create': (C.c_int, [P(NmpcDesc), i32, P(vp)]),

@@ -6,14 +6,15 @@ controller's model], cp=p)`, `plant.simulate(u=u, p=p)`, `observer.estimate()` -
 observer runs alongside.  Here the plant is advanced on the device: with the controller's shooting map when it is the
 controller's own model (`NMPC.plant_step`), with `Model.step` for a plant model of its own (a continuous plant is integrated with
 eight classic Runge-Kutta steps per interval, or - set up with `Model.setup(solver='dopri5')` - under error control like the
-reference's CVODES), or by a callable `(x, u, p) -> x+`."""
+reference's CVODES), or by a callable `(x, u, p) -> x+`.  A controller without `optimize` but with `call` (the LQR) is asked
+`u = controller.call(x=x, p=p)` (control_loop.py:377)."""
 import numpy as np
 import torch
 
 
 class SimpleControlLoop:
     def __init__(self, plant, controller, observer=None):
-        if not hasattr(controller, 'optimize'):
+        if not hasattr(controller, 'optimize') and not hasattr(controller, 'call'):
             raise TypeError("the controller must offer optimize() (NMPC / LMPC)")
         self._controller, self._observer = controller, observer
         if callable(plant) and not hasattr(plant, 'dynamical_state_names'):
@@ -49,7 +50,10 @@ class SimpleControlLoop:
         x = x0 if tensor else np.atleast_2d(np.asarray(x0, dtype=float))
         X, U, S, E = [x], [], [], []
         for _ in range(int(steps)):
-            u = c.optimize(x, cp=p, **kwargs) if p is not None else c.optimize(x, **kwargs)       # control_loop.py:362
+            if hasattr(c, 'optimize'):
+                u = c.optimize(x, cp=p, **kwargs) if p is not None else c.optimize(x, **kwargs)   # control_loop.py:362
+            else:
+                u = c.call(x=x, p=p)                                                              # control_loop.py:377 (LQR)
             st = getattr(c, 'solver_status_code', None)
             S.append(None if st is None else np.asarray(st).copy())
             if self._plant_fun is not None:

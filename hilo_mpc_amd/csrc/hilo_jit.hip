@@ -356,11 +356,11 @@ int jit_nmpc_kernels(const JitRequest& r, int device, JitKernels* out) {
 }
 
 // ---- filters of models written as expressions: kf_body<UserModel, UKF, MODE> behind six extern "C" kernels, the fused / team /
-// particle variants and the roll-out (csrc/hilo_integrate.h::rollout_body) -------------------------------------------------
+// particle variants, the roll-out (csrc/hilo_integrate.h::rollout_body) and the regulator (csrc/hilo_lqr.h) ----------------------
 static std::map<std::string, JitKfKernels> g_kf_loaded;
 
 int jit_kf_kernels(const std::string& user_source, int device, JitKfKernels* out, bool compile_only, bool private_module) {
-  std::string tu = "#include \"hilo_kf_kernel.h\"\n#include \"hilo_integrate.h\"\nextern \"C\" { __device__ const double* hilo_user_gp[4]; }\nnamespace hilo {\n";
+  std::string tu = "#include \"hilo_kf_kernel.h\"\n#include \"hilo_integrate.h\"\n#include \"hilo_lqr.h\"\nextern \"C\" { __device__ const double* hilo_user_gp[4]; }\nnamespace hilo {\n";
   tu += user_source;
   tu += R"(
 }  // namespace hilo
@@ -424,8 +424,24 @@ extern "C" __global__ __launch_bounds__(ROLLOUT_TPB) void hilo_user_rollout(KfPa
                                                                             double* __restrict__ Y, int* __restrict__ stats) {
   rollout_body<UserModel>(kp, sp, batch, steps, x0, up, up_stride, up_step, X, Y, stats);
 }
+extern "C" __global__ __launch_bounds__(64) void hilo_user_lqr_call(KfParams kp, LqrParams o, int64_t batch, const double* __restrict__ x,
+                                                                    const double* __restrict__ x_eq, const double* __restrict__ u_eq,
+                                                                    const double* __restrict__ p, int64_t p_stride,
+                                                                    const double* __restrict__ Q, const double* __restrict__ R,
+                                                                    const double* __restrict__ N, double* __restrict__ K,
+                                                                    double* __restrict__ P, double* __restrict__ u, int* __restrict__ stats) {
+  __shared__ double lqr_lds[LqrModelOk<UserModel>::value ? lqr_work_doubles(UserModel::NX, UserModel::NU) * lqr_lanes(UserModel::NX, UserModel::NU) : 1];
+  lqr_call_body<UserModel>((lds_double*)lqr_lds, kp, o, batch, x, x_eq, u_eq, p, p_stride, Q, R, N, K, P, u, stats);
+}
+extern "C" __global__ __launch_bounds__(64) void hilo_user_lqr_linearize(KfParams kp, int64_t batch, const double* __restrict__ x,
+                                                                         const double* __restrict__ up, int64_t up_stride,
+                                                                         double* __restrict__ A, double* __restrict__ B,
+                                                                         double* __restrict__ C) {
+  lqr_linearize_body<UserModel>(kp, batch, x, up, up_stride, A, B, C);
+}
 extern "C" __global__ void hilo_user_kf_info(int* o) {
   o[0] = UserModel::NX; o[1] = UserModel::NU; o[2] = UserModel::NP; o[3] = UserModel::NY; o[4] = UserModel::DISCRETE ? 1 : 0;
+  o[5] = LqrModelOk<UserModel>::value ? 1 : 0;
 }
 )";
   std::vector<std::string> opts;
@@ -458,13 +474,24 @@ extern "C" __global__ void hilo_user_kf_info(int* o) {
   HILO_HIP_CHECK(hipModuleGetFunction(&k.team[1], mod, "hilo_user_kf_ut"));
   HILO_HIP_CHECK(hipModuleGetFunction(&k.rollout, mod, "hilo_user_rollout"));
   if (hipFuncGetAttribute(&k.rollout_scratch, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, k.rollout) != hipSuccess) k.rollout_scratch = 0;
+  HILO_HIP_CHECK(hipModuleGetFunction(&k.lqr_call, mod, "hilo_user_lqr_call"));
+  HILO_HIP_CHECK(hipModuleGetFunction(&k.lqr_linearize, mod, "hilo_user_lqr_linearize"));
+  {
+    int s1 = 0, s2 = 0;
+    if (hipFuncGetAttribute(&s1, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, k.lqr_call) != hipSuccess) s1 = 0;
+    if (hipFuncGetAttribute(&s2, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, k.lqr_linearize) != hipSuccess) s2 = 0;
+    k.lqr_scratch = s1 > s2 ? s1 : s2;
+  }
   hipFunction_t info = nullptr;
   HILO_HIP_CHECK(hipModuleGetFunction(&info, mod, "hilo_user_kf_info"));
   int* dinfo = nullptr;
   HILO_HIP_CHECK(hipMalloc((void**)&dinfo, sizeof(int) * 8));
   void* args[] = {&dinfo};
   HILO_HIP_CHECK(hipModuleLaunchKernel(info, 1, 1, 1, 1, 1, 1, 0, nullptr, args, nullptr));
-  HILO_HIP_CHECK(hipMemcpy(k.dims, dinfo, sizeof(int) * 5, hipMemcpyDeviceToHost));
+  int hinfo[6];
+  HILO_HIP_CHECK(hipMemcpy(hinfo, dinfo, sizeof(int) * 6, hipMemcpyDeviceToHost));
+  for (int i = 0; i < 5; ++i) k.dims[i] = hinfo[i];
+  k.lqr_ok = hinfo[5];
   HILO_HIP_CHECK(hipFree(dinfo));
   {
     hipDeviceptr_t gptr = nullptr;

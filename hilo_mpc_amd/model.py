@@ -415,6 +415,87 @@ class Model:
     input_matrix = property(lambda s: s.system_matrices()[1])
     output_matrix = property(lambda s: s.system_matrices()[2])
 
+    def _linearization_handle(self, device_index=None):
+        """The filter handle whose map `linearization` and the LQR differentiate on the device.  A linearised copy (`linearize`)
+        carries the nonlinear equations and a mark; its handle is built from a private copy without the mark (`user_source` keeps
+        refusing the marked one: filters, NMPC and simulation need the model itself).  A model without measurement equations
+        gets y = x in that private copy (`system_matrices` hands out C = I for it)."""
+        stamp = (self.dt, self.erk_order, self.n_sub, id(self._ode) if self._symbolic else None, id(self._meas) if self._symbolic else None)
+        h = getattr(self, '_lin_plant', None)
+        if h is None or h._model_stamp != stamp:
+            from .estimator import ExtendedKalmanFilter
+            pm = self
+            if self._symbolic and (getattr(self, '_linearized', False) or not self._meas):
+                pm = copy.copy(self)
+                pm._linearized = False
+                if not pm._meas:
+                    pm._meas, pm.n_y = list(pm.x), pm.n_x
+                    pm.measurement_names = [f'y_{i}' for i in range(pm.n_x)]
+            import warnings
+            with warnings.catch_warnings():
+                warnings.simplefilter('ignore')          # ("the supplied model is linear": the filter is only the handle's carrier)
+                h = ExtendedKalmanFilter(pm, device_index=device_index)
+            h.setup()
+            h._model_stamp = stamp
+            self._lin_plant = h
+        return h
+
+    def linearization(self, x=None, u=None, p=None, device_index=None):
+        """(A, B, C) = (dPhi/dx, dPhi/du, dh/dx) of the discrete-time map x+ = Phi(x, u, p) - the map of `step`, `rollout` and the
+        extended Kalman filter - for a batch of operating points, on the device in forward mode (`hilo_model_linearize`): the
+        device sibling of `system_matrices`.  x [n_x] or [B, n_x] (default: the equilibrium point, else the origin), u and p
+        likewise (p default: `set_initial_parameter_values`); a leading axis of 1 is shared by the batch.  Returns [B, n_x, n_x],
+        [B, n_x, n_u], [B, n_y, n_x] (without the batch axis when no argument had one) - device tensors for device tensors, numpy
+        otherwise.  A continuous model has to be discretised first."""
+        import torch
+        from . import _lib
+        from ._device import ptr, stream_ptr, to_dev
+        if not self._is_setup:
+            raise RuntimeError("Model is not set up. Run Model.setup() before asking for its linearisation.")
+        if not self.discrete:
+            raise NotImplementedError("the Jacobians are those of the discrete-time map: discretize the model first (Model.discretize)")
+        if getattr(self, 'n_z', 0):
+            raise NotImplementedError("linearisation of a model with algebraic states is not built")
+        if self.n_u == 0:
+            raise RuntimeError("The model is autonomous: there is no input matrix.")
+        h = self._linearization_handle(device_index)
+        dev = h._dev
+        tensors = any(isinstance(v, torch.Tensor) for v in (x, u, p))
+        x = getattr(self, '_x_eq', None) if x is None else x
+        u = getattr(self, '_u_eq', None) if u is None else u
+        x = np.zeros(self.n_x) if x is None else x
+        u = np.zeros(self.n_u) if u is None else u
+        if self.name == 'lti':
+            p = self.lti_parameters()
+        elif h._n_p:
+            p = getattr(self, '_p_init', None) if p is None else p
+            if p is None:
+                raise ValueError(f"The model has {self.n_p} parameter(s): {self.parameter_names}. Their values are needed for "
+                                 f"the system matrices (argument `p` / set_initial_parameter_values).")
+        rows, batched = [], False
+        for v, n, what in ((x, self.n_x, 'states'), (u, self.n_u, 'inputs'), (p, h._n_p, 'parameters')):
+            if n == 0:
+                rows.append(None)
+                continue
+            t = to_dev(v, dev)
+            if t.dim() > 2 or (t.dim() == 2 and t.shape[1] != n) or (t.dim() <= 1 and t.numel() != n):
+                raise ValueError(f"{what}: expected [{n}] or [B, {n}], got {list(t.shape)}")
+            batched = batched or t.dim() == 2
+            rows.append(t.reshape(-1, n))
+        B = max(t.shape[0] for t in rows if t is not None)
+        for t, what in zip(rows, ('states', 'inputs', 'parameters')):
+            if t is not None and t.shape[0] not in (1, B):
+                raise ValueError(f"{what}: batch {t.shape[0]} does not match {B}")
+        xt = rows[0].expand(B, -1).contiguous()
+        up = torch.cat([t.expand(B, -1) for t in rows[1:] if t is not None], dim=1).contiguous()
+        ny = h._n_y
+        A = torch.empty(B, self.n_x, self.n_x, dtype=torch.float64, device=dev)
+        Bm = torch.empty(B, self.n_x, self.n_u, dtype=torch.float64, device=dev)
+        Cm = torch.empty(B, ny, self.n_x, dtype=torch.float64, device=dev)
+        _lib.check(_lib.lib().hilo_model_linearize(h._handle, B, ptr(xt), ptr(up), up.shape[1], ptr(A), ptr(Bm), ptr(Cm), stream_ptr(dev)))
+        out = (A, Bm, Cm) if batched else (A[0], Bm[0], Cm[0])
+        return out if tensors else tuple(t.cpu().numpy() for t in out)
+
     def lti_parameters(self):
         return np.concatenate([self.A.ravel(), self.B.ravel(), self.C.ravel()])
 
@@ -579,6 +660,7 @@ class Model:
         m = copy.copy(self)
         m._sim = None              # the copy simulates its own trajectory
         m._rollout_up = None       # ... with its own buffer for the packed inputs and parameters
+        m._lin_plant = None        # ... and its own handle for `linearization`
         if hasattr(self, '_gps'):
             m._gps = list(self._gps)    # learned terms substituted into the copy later must not appear in the original
         if getattr(self, '_gp_helpers', None):

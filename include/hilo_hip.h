@@ -201,6 +201,54 @@ int hilo_model_rollout(hilo_kf* kf, const hilo_sim_opts* opts, int64_t batch, in
                        void* stream);
 
 /* ------------------------------------------------------------------------------------------------------- */
+/* Linear-quadratic regulator: batched linearisation, Riccati gains and feedback                            */
+/* replaces `LinearQuadraticRegulator.setup / call` (hilo_mpc/modules/controller/lqr.py:204-306)            */
+/* ------------------------------------------------------------------------------------------------------- */
+/* The gain of x+ = A x + B u under the cost sum x'Qx + u'Ru + 2 x'Nu, one instance per lane (csrc/hilo_lqr.h):
+     horizon > 0   lqr.py:236-245: from P = Q, `horizon` steps P <- A'PA - (A'PB + N)(R + B'PB)^-1 (B'PA + N') + Q, then
+                   K = (R + B'PB)^-1 (B'PA + N')  (Cholesky factorisation of R + B'PB)
+     horizon = 0   the stationary gain (the reference: NotImplementedError): the discrete algebraic Riccati equation by the
+                   structure-preserving doubling algorithm, at most max_iter steps, until max|H+ - H| <= tol max(1, max|H+|)
+   Per-instance status: 0 ok; HILO_LQR_STATUS_MAX_ITER: max_iter doubling steps without convergence; HILO_LQR_STATUS_FAILED: an iterate
+   that is not finite, a singular I + G H, or R + B'PB not positive definite.  An instance with a non-zero status gets NaN rows in K, P
+   and u; the other instances are not affected and the call returns HILO_OK.  stats [B][2] int32: status, steps made.
+   All matrices row-major.  HILO_ENOTSUP for more than HILO_LQR_MAX_NX states or HILO_LQR_MAX_NU inputs, for a handle whose model is
+   continuous and was not discretised (the gains are discrete-time), for a model without inputs or with algebraic states, and for
+   a run-time compiled model whose kernels need scratch memory. */
+#define HILO_LQR_MAX_NX 8
+#define HILO_LQR_MAX_NU 4
+#define HILO_LQR_STATUS_OK 0
+#define HILO_LQR_STATUS_MAX_ITER 1
+#define HILO_LQR_STATUS_FAILED 2
+typedef struct hilo_lqr_opts {
+  int32_t horizon;   /* backward Riccati steps; 0 = stationary */
+  int32_t max_iter;  /* doubling steps (<= 0: 50) */
+  double tol;        /* (<= 0: 1e-12) */
+} hilo_lqr_opts;
+/* A = dPhi/dx [B][nx][nx], B = dPhi/du [B][nx][nu] and, unless NULL, C = dh/dx [B][ny][nx] of the handle's map x+ = Phi(x, u, p) - the
+   one of hilo_pf_function, hilo_model_rollout and the extended Kalman filter - at x [B][nx] and the rows [u; p] of `up` (up_stride
+   between instances, 0: shared), in forward mode. */
+int hilo_model_linearize(hilo_kf* kf, int64_t batch, const double* x, const double* up, int64_t up_stride, double* A,
+                         double* B, double* C, void* stream);
+/* Gains from given matrices (no handle; on the current device): A [nx][nx], B [nx][nu], Q [nx][nx], R [nu][nu], N [nx][nu] (NULL: zero)
+   of instance b at A + b a_stride, ... (a stride of 0: shared by the batch); opts NULL: stationary with the defaults.
+   K [B][nu][nx]; P [B][nx][nx] the Riccati solution, or NULL; stats or NULL. */
+int hilo_lqr_gain(int nx, int nu, int64_t batch, const double* A, int64_t a_stride, const double* B, int64_t b_stride,
+                  const double* Q, int64_t q_stride, const double* R, int64_t r_stride, const double* N, int64_t n_stride,
+                  const hilo_lqr_opts* opts, double* K, double* P, int32_t* stats, void* stream);
+/* Linearise, gain and feedback in ONE launch (the gain-scheduled path): the Jacobians of the handle's map at the operating point
+   x_eq [B][nx], u_eq [B][nu] (NULL: the origin) with the parameters p (rows of np, p_stride between instances, 0: shared), the gain
+   for Q, R, N (shared by the batch; N NULL: zero), and u [B][nu] = u_eq - K (x - x_eq) for x [B][nx].  x and u both NULL: the
+   gains alone.  K, P, stats as above. */
+int hilo_lqr_call(hilo_kf* kf, const hilo_lqr_opts* opts, int64_t batch, const double* x, const double* x_eq,
+                  const double* u_eq, const double* p, int64_t p_stride, const double* Q, const double* R, const double* N,
+                  double* K, double* P, double* u, int32_t* stats, void* stream);
+/* u [B][nu] = u_eq - K (x - x_eq) with a gain computed before: K at K + b k_stride (0: one gain for the batch); x_eq, u_eq [B][.] or
+   NULL (zero). */
+int hilo_lqr_apply(int nx, int nu, int64_t batch, const double* K, int64_t k_stride, const double* x, const double* x_eq,
+                   const double* u_eq, double* u, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------- */
 /* Gaussian process: exact inference + prediction                                                           */
 /* replaces `ca.Function('prediction',[X,w,p],[mean,var])` (hilo_mpc/modules/machine_learning/gp/gp.py:      */
 /* 623-629, called from `predict` gp.py:709) whose body is `ExactInference.get_posterior`                   */

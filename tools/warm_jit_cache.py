@@ -25,6 +25,7 @@ def main(argv):
                      '-W', 'ignore', '-n', jobs] + sel, cwd=ROOT, env=env, stdout=subprocess.DEVNULL)
     if not argv:
         subprocess.call([sys.executable, os.path.abspath(__file__), '--learned-filter'], cwd=ROOT, env=env)
+        subprocess.call([sys.executable, os.path.abspath(__file__), '--lqr'], cwd=ROOT, env=env)
     after = set(os.listdir(cache)) if os.path.isdir(cache) else set()
     print(f"{len(after - before)} new code object(s), {len(after)} in {cache}")
     # the backend's EXEC-prologue defect shows up in run-time compiled problems as well: check what was compiled
@@ -52,8 +53,21 @@ def learned_filter():
         gp._handle = None                            # (nothing to destroy)
 
 
+def lqr():
+    """The regulator's set-ups of tests/test_lqr_gpu.py and tools/bench_lqr.py: `LQR.setup()` compiles the filter unit of its model
+    (the regulator's two kernels are part of it) and stops."""
+    sys.path.insert(0, ROOT)
+    from hilo_mpc_amd import LQR
+    from tests import lqr_reference as lr
+    for m in (lr.reference_model(), lr.bicycle().linearize(), lr.pendulum().linearize()):
+        LQR(m).setup()
+
+
 if __name__ == '__main__':
     if sys.argv[1:] == ['--learned-filter']:
         learned_filter()
+        sys.exit(0)
+    if sys.argv[1:] == ['--lqr']:
+        lqr()
         sys.exit(0)
     sys.exit(main(sys.argv[1:]))
