@@ -33,7 +33,9 @@ from .control_loop import SimpleControlLoop
 from .pf import ParticleFilter
 from .lqr import LinearQuadraticRegulator, LQR
 
+from .ann import ArtificialNeuralNetwork, ANN, Layer, Dense, Dropout
+
 PF = ParticleFilter
 
 __all__ += ['NMPC', 'SMPC', 'MovingHorizonEstimator', 'MHE', 'LMPC', 'expr', 'SimpleControlLoop', 'ParticleFilter', 'PF',
-            'LinearQuadraticRegulator', 'LQR']
+            'LinearQuadraticRegulator', 'LQR', 'ArtificialNeuralNetwork', 'ANN', 'Layer', 'Dense', 'Dropout']

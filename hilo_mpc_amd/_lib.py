@@ -149,6 +149,9 @@ def _declare(lib):
         'hilo_gp_predict': (C.c_int, [vp, i64, vp, i32, vp, vp, vp]),
         'hilo_gp_kernel_matrix': (C.c_int, [i32, i32, vp, i32, i64, vp, i64, vp, vp, vp]),
         'hilo_gp_mean': (C.c_int, [i32, i32, vp, i32, i64, vp, vp, vp]),
+        'hilo_ann_create': (C.c_int, [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, P(vp)]),
+        'hilo_ann_destroy': (None, [vp]),
+        'hilo_ann_predict': (C.c_int, [vp, i64, vp, i64, vp, i64, vp]),
     }
     for name, (res, args) in sig.items():
         if not hasattr(lib, name):

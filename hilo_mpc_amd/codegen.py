@@ -132,9 +132,11 @@ def gp_helper_source(k, nf, kexpr):
             f"  return g[3] + acc;\n}}\n")
 
 
-def model_source(n_x, n_u, n_p, ode, meas, discrete, helpers=()):
+def model_source(n_x, n_u, n_p, ode, meas, discrete, helpers=(), symbolic=True, lqr_chunk=None):
     """`struct UserModel` for the right-hand side `ode` (list of n_x expressions) and the measurement map `meas`; `helpers`:
-    source of the functions the expressions call (learned terms with general kernels)."""
+    source of the functions the expressions call (learned terms with general kernels); symbolic=False leaves the symbolic
+    derivative source out (a large network inside the model, Model.ANN_SYM_NODES: the engine keeps its Taylor sweeps); lqr_chunk: forward-mode
+    directions per pass of the linearisation kernels (csrc/hilo_lqr.h::LqrChunk; None = all of them up to six)."""
     if len(ode) != n_x:
         raise ValueError(f"the model has {n_x} states but {len(ode)} dynamical equations")
     em = Emitter()
@@ -147,7 +149,8 @@ def model_source(n_x, n_u, n_p, ode, meas, discrete, helpers=()):
     src = (''.join(helpers) +
            f"struct UserModel {{\n"
            f"  static constexpr int NX = {n_x}, NU = {n_u}, NP = {n_p}, NY = {n_y};\n"
-           f"  static constexpr bool DISCRETE = {'true' if discrete else 'false'};\n"
+           f"  static constexpr bool DISCRETE = {'true' if discrete else 'false'};\n" +
+           (f"  static constexpr int LQR_CHUNK = {int(lqr_chunk)};\n" if lqr_chunk else "") +
            f"  template <class T, class U, class P>\n"
            f"  __device__ __forceinline__ static void ode(const T* x, const U* u, const P* p, double dt, T* dx) {{\n"
            f"    (void)x; (void)u; (void)p; (void)dt;\n" + '\n'.join(body) + "\n  }\n"
@@ -157,7 +160,7 @@ def model_source(n_x, n_u, n_p, ode, meas, discrete, helpers=()):
     # symbolic first / second derivatives for the engine's derivative phase (csrc/hilo_ocp.h::eval_derivs_sym); a model with
     # a learned term keeps the Taylor sweeps
     learned = ('gp', 'gpvar', 'gpd', 'gpk')
-    if not any(n.op in learned for e in ode for n in Expr.wrap(e).nodes().values()):
+    if symbolic and not any(n.op in learned for e in ode for n in Expr.wrap(e).nodes().values()):
         from .symdiff import sym_source
         src += sym_source('UserModel', n_x, n_u, ode,
                           meas if not any(n.op in learned for e in meas for n in Expr.wrap(e).nodes().values()) else None)

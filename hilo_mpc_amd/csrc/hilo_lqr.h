@@ -289,7 +289,31 @@ HD int lqr_solve(int n, int m, const LqrParams& o, const LqrWork<V>& w, const do
 
 // Directions of one forward-mode pass: all NX + NU at once up to six (the zoo: at most 4 + 2), otherwise passes of four - the
 // slopes of the Runge-Kutta step carry (1 + directions) doubles per state.
-template <class M> struct LqrChunk { static constexpr int value = M::NX + M::NU <= 6 ? (M::NX + M::NU > 0 ? M::NX + M::NU : 1) : 4; };
+// A functor may ask for narrower passes with `static constexpr int LQR_CHUNK` (emitted for models that carry a neural network:
+// every value of the network is multiplied by 1 + directions, and with all six the Runge-Kutta step no longer fits the registers).
+// The Jacobian columns do not depend on how they are grouped.
+template <class M, class = void> struct LqrChunkHint { static constexpr int value = 0; };
+template <class M> struct LqrChunkHint<M, decltype((void)M::LQR_CHUNK)> { static constexpr int value = M::LQR_CHUNK; };
+template <class M> struct LqrChunk {
+  static constexpr int full = M::NX + M::NU <= 6 ? (M::NX + M::NU > 0 ? M::NX + M::NU : 1) : 4;
+  static constexpr int value = LqrChunkHint<M>::value > 0 && LqrChunkHint<M>::value < full ? LqrChunkHint<M>::value : full;
+};
+
+// The passes of a functor that asked for narrower ones are unrolled like any (the unit seeds stay constants, and most products with
+// them fold away), but they are kept apart: each pass reads its operating point through a value the compiler cannot see through -
+// otherwise every value of the first pass, the same in all passes, is kept alive for the later ones - and a scheduling fence
+// follows it.  HINT = 0: nothing happens.
+template <int HINT> HD double lqr_pass_value(double v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  if constexpr (HINT > 0) asm volatile("" : "+v"(v));
+#endif
+  return v;
+}
+template <int HINT> HD void lqr_pass_fence() {
+#if defined(__HIP_DEVICE_COMPILE__)
+  if constexpr (HINT > 0) __builtin_amdgcn_sched_barrier(0);
+#endif
+}
 
 // A = dPhi/dx (NX x NX), B = dPhi/du (NX x NU) of Phi = model_step<M>(order, nsub, .) - the map of the handle's step, roll-out and
 // extended Kalman filter - and, with WANT_C, C = dh/dx (NY x NX), at (x, u, p); A, B, C: any indexable views, row-major.
@@ -302,13 +326,13 @@ HD void lqr_linearize(int order, int nsub, const double* x, const double* u, con
     D xd[NX], ud[NU > 0 ? NU : 1], xn[NX];
 #pragma unroll
     for (int i = 0; i < NX; ++i) {
-      xd[i] = D(x[i]);
+      xd[i] = D(lqr_pass_value<LqrChunkHint<M>::value>(x[i]));
 #pragma unroll
       for (int j = 0; j < CH; ++j) xd[i].d[j] = (i == base + j) ? 1.0 : 0.0;
     }
 #pragma unroll
     for (int i = 0; i < NU; ++i) {
-      ud[i] = D(u[i]);
+      ud[i] = D(lqr_pass_value<LqrChunkHint<M>::value>(u[i]));
 #pragma unroll
       for (int j = 0; j < CH; ++j) ud[i].d[j] = (NX + i == base + j) ? 1.0 : 0.0;
     }
@@ -332,6 +356,7 @@ HD void lqr_linearize(int order, int nsub, const double* x, const double* u, con
             if (base + j < NX) C[i * NX + base + j] = yd[i].d[j];
       }
     }
+    lqr_pass_fence<LqrChunkHint<M>::value>();
   }
 }
 

@@ -281,10 +281,14 @@ class Model:
             if self.n_z:
                 if self._native_discrete:
                     raise NotImplementedError("algebraic states of a discrete model are not built")
+                # a network inside a model with algebraic states: the symbolic source and the LQR_CHUNK hint of the branch below are
+                # not passed on - `linearization` / LQR differentiate such a model in one pass
                 return codegen.dae_model_source(self.n_x, self.n_u, self.n_p, self.n_z, self._ode, self._alg, self._meas,
                                                 z_guess if z_guess is not None else [0.] * self.n_z, alg_at_slope=alg_at_slope)
             helpers = [src for _, src in sorted(getattr(self, '_gp_helpers', {}).items())]
-            return codegen.model_source(self.n_x, self.n_u, self.n_p, self._ode, self._meas, self._native_discrete, helpers=helpers)
+            ann_nodes = sum(a.n_nodes() for a in getattr(self, '_anns', None) or [])
+            return codegen.model_source(self.n_x, self.n_u, self.n_p, self._ode, self._meas, self._native_discrete, helpers=helpers,
+                                        symbolic=ann_nodes <= self.ANN_SYM_NODES, lqr_chunk=self.ANN_LQR_CHUNK if ann_nodes else None)
         if self.name == 'lti':
             return codegen.zoo_alias(f"Lti<{self.n_x}, {self.n_u}, {self.n_y}>")
         if self.name not in ZOO_FUNCTOR:
@@ -569,8 +573,14 @@ class Model:
             for o in obj:
                 self.substitute_from(o)
             return self
+        from .ann import ArtificialNeuralNetwork
         if self._symbolic:
+            if isinstance(obj, ArtificialNeuralNetwork):
+                return self._substitute_ann(obj)
             return self._substitute_symbolic(obj)
+        if isinstance(obj, ArtificialNeuralNetwork):
+            raise NotImplementedError(f"model '{self.name}' is a model of the device zoo: a neural network is substituted into models "
+                                      f"written as expressions (Model.set_dynamical_equations)")
         if self.name not in LEARNABLE:
             raise NotImplementedError(f"model '{self.name}' has no learnable term in the device zoo "
                                       f"(available: {sorted(LEARNABLE)})")
@@ -656,6 +666,75 @@ class Model:
         self._is_setup = False
         return self
 
+    # Size limits of a network written into a model as expressions, in neurons (hidden nodes + labels; DESIGN.md 5.3b has the
+    # compile measurements behind them): above ANN_SYM_NODES the symbolic first / second derivative source is left out and the
+    # engine keeps its Taylor sweeps (as for GP terms); above ANN_MAX_NODES the substitution is refused.  Both count the neurons of
+    # all networks of the model together, as `user_source` emits them together.
+    ANN_SYM_NODES = 24
+    ANN_LQR_CHUNK = 3           # forward-mode directions per pass of `linearization` / LQR on a model that carries a network
+    ANN_MAX_NODES = 56
+
+    def _substitute_ann(self, ann):
+        """A neural network as a learned term (dynamic_model.py:3040-3125 with util/machine_learning.py:521-578
+        `net_to_casadi_graph`): every label must be a parameter, all of them leave the parameter vector; the features are states,
+        inputs or remaining parameters, looked up by name.  The network becomes part of the expressions - weights as numbers,
+        hidden activations shared between the labels - so the model stays an ordinary expression model for every consumer."""
+        labels, features = list(ann.labels), list(ann.features)
+        if not ann.is_trained():
+            raise RuntimeError("The ANN has not been trained yet. Hand the weights over with load_torch() or set_weights().")
+        if self._ode is None:
+            raise RuntimeError("set the model equations before substituting a learned term")
+        if len(set(labels)) != len(labels):
+            raise ValueError(f"duplicate labels in {labels}")
+        for lb in labels:
+            if lb not in self.parameter_names:
+                raise ValueError(f"label '{lb}' is not a parameter of model '{self.name}' (parameters: "
+                                 f"{self.parameter_names})")
+        have = sum(a.n_nodes() for a in getattr(self, '_anns', None) or [])
+        if have + ann.n_nodes() > self.ANN_MAX_NODES:
+            raise NotImplementedError(f"a network of {ann.n_nodes()} neurons (hidden nodes + labels) inside a model" +
+                                      (f" that already holds {have}" if have else "") +
+                                      f": at most {self.ANN_MAX_NODES} are compiled into the model's right-hand side")
+        keep = [n for n in self.parameter_names if n not in labels]
+        newp = SymVector('p', keep)
+        feats = []
+        for f in features:
+            if f in labels:
+                raise ValueError(f"feature '{f}' is the label itself")
+            for vec in (self.x, self.u, newp):
+                if f in vec._names:
+                    feats.append(vec[f])
+                    break
+            else:
+                raise ValueError(f"feature '{f}' is not a state, input or parameter of model '{self.name}'")
+        out_exprs = ann.expressions(feats)
+        old = list(self.parameter_names)
+        repl = {old.index(lb): e for lb, e in zip(labels, out_exprs)}
+        newidx = {old.index(n): newp[q] for q, n in enumerate(keep)}
+
+        def leaf(n):
+            if n.op != 'p':
+                return None
+            i = int(n.value)
+            if i in repl:
+                return repl[i]
+            return newidx[i] if int(newidx[i].value) != i else None
+
+        # every equation list that can hold a parameter leaf is re-indexed together (the algebraic equations too).  The network's
+        # nodes are younger than the user's statements; Expr.substitute rebuilds in creation order, so they must be passed through
+        # as they are: the rebuilt equations only refer to them.
+        alg = list(getattr(self, '_alg', None) or [])
+        neq, nalg = len(self._ode), len(alg)
+        out = Expr.substitute(self._ode + alg + self._meas, leaf)
+        self._ode, self._meas = out[:neq], out[neq + nalg:]
+        if nalg:
+            self._alg = out[neq:neq + nalg]
+        self.parameter_names, self.n_p = keep, len(keep)
+        self._anns = list(getattr(self, '_anns', None) or []) + [ann]
+        self._is_setup = False
+        self._linear = self._check_linearity()
+        return self
+
     def copy(self, setup=True):
         m = copy.copy(self)
         m._sim = None              # the copy simulates its own trajectory
@@ -665,6 +744,8 @@ class Model:
             m._gps = list(self._gps)    # learned terms substituted into the copy later must not appear in the original
         if getattr(self, '_gp_helpers', None):
             m._gp_helpers = dict(self._gp_helpers)
+        if getattr(self, '_anns', None):
+            m._anns = list(self._anns)
         return m
 
     # ---- the model as a PLANT: one sampling interval for a batch of states (dynamic_model.py:3360-3400, :3911-4000) -----------------

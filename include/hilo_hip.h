@@ -641,6 +641,37 @@ int hilo_qp_solve_pinned(hilo_qp* h, int64_t batch, const double* H, int64_t h_s
                          int64_t ba_stride, double* x, double* f, double* lam_a, double* lam_x, int32_t* status, int32_t* iters,
                          void* stream);
 
+/* ------------------------------------------------------------------------------------------------------- */
+/* ANN: batched inference of a feed-forward network                                                         */
+/* replaces `ArtificialNeuralNetwork.predict` (hilo_mpc/modules/machine_learning/nn/nn.py:536-544): input     */
+/* scaling (x - mean) / scale, dense layers h <- act(W h + b), a linear output layer, output scaling           */
+/* y * scale + mean - the chain `net_to_casadi_graph` writes (util/machine_learning.py:521-578).             */
+/* One fused kernel on the f64 matrix cores (csrc/hilo_ann.hip); training stays with the caller's framework.   */
+/* ------------------------------------------------------------------------------------------------------- */
+#define HILO_ANN_ACT_LINEAR 0
+#define HILO_ANN_ACT_SIGMOID 1
+#define HILO_ANN_ACT_TANH 2
+#define HILO_ANN_ACT_RELU 3
+#define HILO_ANN_ACT_SOFTPLUS 4
+#define HILO_ANN_MAX_FEATURES 32
+#define HILO_ANN_MAX_LABELS 16
+#define HILO_ANN_MAX_WIDTH 64
+#define HILO_ANN_MAX_HIDDEN 8
+#define HILO_ANN_MAX_LDS_BYTES 131072   /* staged weights + biases + scaling vectors of one network */
+typedef struct hilo_ann hilo_ann;
+/* The network has n_hidden + 1 dense maps: hidden layer l (widths[l] neurons, activation acts[l]) and the linear output layer.
+   Weights and biases arrive zero padded, map after map: W_l row-major [n_out_pad][n_in_pad] (the `nn.Linear` orientation),
+   b_l [n_out_pad], with n_out_pad = widths[l] rounded up to 16 (16 for the output layer), n_in_pad = nf rounded up to 4 for the
+   first map and the n_out_pad of the map before otherwise.  x_mean / x_scale [nf], y_mean / y_scale [nl]: host vectors, a NULL
+   pair = no scaling.  HILO_ENOTSUP beyond the limits above. */
+int hilo_ann_create(int device, int nf, int nl, int n_hidden, const int32_t* widths, const int32_t* acts,
+                    const double* W_packed, const double* b_packed, const double* x_mean, const double* x_scale,
+                    const double* y_mean, const double* y_scale, hilo_ann** out);
+void hilo_ann_destroy(hilo_ann* h);
+/* Y [nl][m] (row pitch ldy) = network(X [nf][m] (row pitch ldx)): device pointers, queries along the unit stride.  A query's
+   result depends on its own column only and not on m or on its position in the batch. */
+int hilo_ann_predict(hilo_ann* h, int64_t m, const double* X, int64_t ldx, double* Y, int64_t ldy, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
