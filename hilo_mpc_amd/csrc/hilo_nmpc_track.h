@@ -65,6 +65,10 @@ struct NmpcTrack {
     for (int i = 0; i < NX; ++i) z[i] = x[i] - pc.cost[O_ZREF + i];
 #pragma unroll
     for (int i = 0; i < NU; ++i) z[NX + i] = u[i] - pc.cost[O_ZREF + NX + i];
+    // MIRRORED in stage_cost_request / stage_cost_requested below (the values-only pass of the symbolic path): the two must form
+    // the same products and add them in the same order - the objective of a trial point must not depend on which of the two
+    // formed it - so a change here is made there too.  (stage_cost itself keeps its two-row regions: its other callers have no reads to put beside them, and
+    // all 36 weights at once cost them registers.)
     // the weights of two rows are requested from LDS before the first multiply-add (the empty statement with side effects ends
     // the scheduling region; left alone the compiler reads - waits - uses entry by entry, 70 cycles each at one wave per SIMD)
     T acc = T(0.0);
@@ -93,6 +97,50 @@ struct NmpcTrack {
 #pragma unroll
       for (int i = 0; i < NU; ++i) {
         T s = T(0.0);
+#pragma unroll
+        for (int j = 0; j < NU; ++j) s = s + pc.cost[O_WDU + i * NU + j] * d[j];
+        acc = acc + d[i] * s;
+      }
+    }
+    return acc;
+  }
+
+  // stage_cost in two halves, for a caller that has reads of its own to put next to these (the values-only pass of the symbolic
+  // path): ALL weights, the references and the switch of the change penalty requested from LDS in one go, then - same products,
+  // same order of the sums as stage_cost - the value from those registers.
+  struct StageW { double w[NZ][NZ], zr[NZ], hasdu; };
+  __device__ __forceinline__ static void stage_cost_request(const OcpConst& pc, StageW& q) {
+#pragma unroll
+    for (int i = 0; i < NZ; ++i) {
+      q.zr[i] = pc.cost[O_ZREF + i];
+#pragma unroll
+      for (int j = 0; j < NZ; ++j) q.w[i][j] = pc.cost[O_WZ + i * NZ + j];
+    }
+    q.hasdu = pc.cost[O_HASDU];
+    asm volatile("");
+  }
+  __device__ __forceinline__ static double stage_cost_requested(const OcpConst& pc, const double* par, int k, const double* x,
+                                                                const double* u, const StageW& q) {
+    double z[NZ];
+#pragma unroll
+    for (int i = 0; i < NX; ++i) z[i] = x[i] - q.zr[i];
+#pragma unroll
+    for (int i = 0; i < NU; ++i) z[NX + i] = u[i] - q.zr[NX + i];
+    double acc = 0.0;
+#pragma unroll
+    for (int i = 0; i < NZ; ++i) {
+      double s = 0.0;
+#pragma unroll
+      for (int j = 0; j < NZ; ++j) s = s + q.w[i][j] * z[j];
+      acc = acc + z[i] * s;
+    }
+    if (k == 0 && q.hasdu != 0.0) {
+      double d[NU > 0 ? NU : 1];
+#pragma unroll
+      for (int i = 0; i < NU; ++i) d[i] = u[i] - par[M::NP + i];
+#pragma unroll
+      for (int i = 0; i < NU; ++i) {
+        double s = 0.0;
 #pragma unroll
         for (int j = 0; j < NU; ++j) s = s + pc.cost[O_WDU + i * NU + j] * d[j];
         acc = acc + d[i] * s;

@@ -613,12 +613,30 @@ struct Ocp {
 #ifdef HILO_DBG_TWICE_VALS   // developer knob (tools/dbg/c5dae_twice.sh): the same work again - the launch's extra time is this part's cost
     if constexpr (XCW > 0) PB::template coll_pass<false>(pc, (const double*)l.par, (const double*)l.sd, Zp, l.lam, l.cnu, N, l.xc, l.prep, l.prepl);
 #endif
+    // SYM: the wave-uniform inputs of the stage-point routine, once for the pass (see sym_tab)
+    double vpar[NPAR], vsz[NZ], visz[NX];
+    SymTab vtb = SymTab();
+    int vorder = 1;
+    double vh = 0.0;
+    if constexpr (SYM) {
+      sym_par(l.par, vpar);
+#pragma unroll
+      for (int i = 0; i < NZ; ++i) vsz[i] = pc.sz[i];
+#pragma unroll
+      for (int i = 0; i < NX; ++i) visz[i] = rcp_fast(vsz[i]);
+      // (the scalings stay in vector registers here, unlike sz / isz of eval_derivs_sym: with uni() the 20 scalar registers
+      // more than this function has free come back as SGPR-to-lane spills - chemostat4, order 4: 730 instead of 679 instructions,
+      // 13 v_writelane / 37 v_readlane instead of 0 / 24, two scratch accesses, and the kernel's scratch grows by 8 bytes)
+      vorder = PB::Model::DISCRETE ? 1 : uni(pc.order);
+      vh = uni(pc.dt);
+      vtb = sym_tab<PB::Model::DISCRETE>(vorder, vh);
+    }
     OCP_FOR(k, (N) + 1) {
       double x[NX], u[NU > 0 ? NU : 1];
 #pragma unroll
       for (int i = 0; i < NX; ++i) x[i] = Zp[k * NZ + i];
       if (k < N) {
-        double xn[NX];
+        double xn[NX], zn[NX];
 #pragma unroll
         for (int i = 0; i < NU; ++i) u[i] = Zp[k * NZ + NX + i];
         double dvf[NC > 0 ? NC : 1];
@@ -632,21 +650,30 @@ struct Ocp {
         } else if constexpr (SYM) {
           // the derivative phase's own stage-point routine; the points are kept (l.Xs) for the derivative phase that follows
           // when this trial point is accepted
+          // Reads first: the next slot's states (the defects below) and the stage cost's weights are requested together with the
+          // point itself, in front of the integration - behind the stores of the stage points and of the defects, which may alias
+          // them for the compiler, each was a read - wait - use trip of its own.  The stage cost only needs the point: it is
+          // formed at once (the weights do not stay in registers over the integration) and added where it was added.
           using M = typename PB::Model;
           double xp[NX], up[NU > 0 ? NU : 1], X[4][NX], phi[NX];
 #pragma unroll
-          for (int i = 0; i < NX; ++i) xp[i] = x[i] * pc.sz[i];
+          for (int i = 0; i < NX; ++i) zn[i] = Zp[(k + 1) * NZ + i];
+          typename PB::StageW sw;
+          PB::stage_cost_request(pc, sw);
+          const double lk = PB::stage_cost_requested(pc, vpar, k, x, u, sw);
 #pragma unroll
-          for (int i = 0; i < NU; ++i) up[i] = u[i] * pc.sz[NX + i];
-          sym_points<M>(M::DISCRETE ? 1 : pc.order, pc.dt, xp, up, (const double*)l.par, X, phi);
+          for (int i = 0; i < NX; ++i) xp[i] = x[i] * vsz[i];
+#pragma unroll
+          for (int i = 0; i < NU; ++i) up[i] = u[i] * vsz[NX + i];
+          sym_points<M>(vorder, vh, vtb, xp, up, vpar, X, phi);
           dp xs = l.Xs + (size_t)k * 4 * NX;
 #pragma unroll
           for (int i = 0; i < 4; ++i)
 #pragma unroll
             for (int q = 0; q < NX; ++q) xs[i * NX + q] = X[i][q];
 #pragma unroll
-          for (int i = 0; i < NX; ++i) xn[i] = phi[i] * rcp_fast(pc.sz[i]);
-          fpart += PB::stage_cost(pc, (const double*)l.par, sd_of(l, k), k, x, u);
+          for (int i = 0; i < NX; ++i) xn[i] = phi[i] * visz[i];
+          fpart += lk;
         } else {
           if constexpr (SYM_MHE) {   // the arithmetic of the derivative phase (division = x * rcp_fast(y)): same defects in both
             FastD xf[NX], uf[NU > 0 ? NU : 1], xnf[NX];
@@ -664,7 +691,10 @@ struct Ocp {
         }
 #pragma unroll
         for (int i = 0; i < NX; ++i) {
-          const double ci = Zp[(k + 1) * NZ + i] - xn[i];
+          double zi;
+          if constexpr (SYM) zi = zn[i];
+          else zi = Zp[(k + 1) * NZ + i];
+          const double ci = zi - xn[i];
           cp[k * NX + i] = ci;
           tpart += fabs(ci);
         }
@@ -1065,14 +1095,30 @@ struct Ocp {
   // Runge-Kutta stage points X_i and the integrated state Phi of one interval (SYM policies: the tableau of orders 1..4 written
   // out, model divisions as x * rcp_fast(y)): ONE routine for the values-only pass of the line search and for the derivative
   // phase, so that a trial point the line search accepted leaves exactly the stage points the derivative phase needs (l.Xs)
-  template <class M>
-  __device__ __forceinline__ static void sym_points(int order, double h, const double* x, const double* u, const double* par,
-                                                    double (*X)[NX], double* phi) {
-    constexpr bool DISC = M::DISCRETE;
+  // The step-size products of the tableau (orders 1..4, modeling.py:1239-1250: a10, a20, a21, a32 can be non-zero) and the model
+  // parameters are the same in every lane and every stage: a phase forms / reads them ONCE (sym_tab, sym_par) and keeps them in
+  // scalar registers.  Read through `pc` / `l.par` inside the stages they were re-read from LDS in front of every stage - the
+  // stores between the stages may alias them for the compiler - and the stage waited for them (one wave per SIMD: an estimated 50-100 clocks each, the LDS issue-to-use latency; not
+  // measured per read - DESIGN.md 5.1 has the measured clocks of the phase).
+  struct SymTab { double ha10, ha20, ha21, ha32, hb[4]; };
+  template <bool DISC>
+  __device__ __forceinline__ static SymTab sym_tab(int order, double h) {
     const double a10 = order >= 2 ? 0.5 : 0.0, a20 = order == 3 ? -1.0 : 0.0, a21 = order == 3 ? 2.0 : (order == 4 ? 0.5 : 0.0),
                  a32 = order == 4 ? 1.0 : 0.0;
-    const double hb[4] = {DISC ? 1.0 : h * erk_b<0>(order), DISC ? 0.0 : h * erk_b<1>(order), DISC ? 0.0 : h * erk_b<2>(order),
-                          DISC ? 0.0 : h * erk_b<3>(order)};
+    return SymTab{uni(h * a10), uni(h * a20), uni(h * a21), uni(h * a32),
+                  {uni(DISC ? 1.0 : h * erk_b<0>(order)), uni(DISC ? 0.0 : h * erk_b<1>(order)), uni(DISC ? 0.0 : h * erk_b<2>(order)),
+                   uni(DISC ? 0.0 : h * erk_b<3>(order))}};
+  }
+  template <class LP>
+  __device__ __forceinline__ static void sym_par(LP lpar, double* parv) {
+#pragma unroll
+    for (int i = 0; i < NPAR; ++i) parv[i] = i < PB::NPAR ? uni(lpar[i < PB::NPAR ? i : 0]) : 0.0;
+  }
+
+  template <class M>
+  __device__ __forceinline__ static void sym_points(int order, double h, const SymTab& tb, const double* x, const double* u,
+                                                    const double* par, double (*X)[NX], double* phi) {
+    constexpr bool DISC = M::DISCRETE;
     FastD kk[4][NX], uf[NU > 0 ? NU : 1];
 #pragma unroll
     for (int i = 0; i < NU; ++i) uf[i] = FastD(u[i]);
@@ -1082,9 +1128,9 @@ struct Ocp {
 #pragma unroll
       for (int s = 0; s < NX; ++s) {
         double acc = x[s];
-        if (i == 1) acc += (h * a10) * kk[0][s].v;
-        if (i == 2) acc += (h * a20) * kk[0][s].v + (h * a21) * kk[1][s].v;
-        if (i == 3) acc += (h * a32) * kk[2][s].v;
+        if (i == 1) acc += tb.ha10 * kk[0][s].v;
+        if (i == 2) acc += tb.ha20 * kk[0][s].v + tb.ha21 * kk[1][s].v;
+        if (i == 3) acc += tb.ha32 * kk[2][s].v;
         X[i][s] = acc;
         Xf[s] = FastD(acc);
       }
@@ -1097,7 +1143,7 @@ struct Ocp {
     }
 #pragma unroll
     for (int s = 0; s < NX; ++s)
-      phi[s] = (DISC ? 0.0 : x[s]) + hb[0] * kk[0][s].v + hb[1] * kk[1][s].v + hb[2] * kk[2][s].v + hb[3] * kk[3][s].v;
+      phi[s] = (DISC ? 0.0 : x[s]) + tb.hb[0] * kk[0][s].v + tb.hb[1] * kk[1][s].v + tb.hb[2] * kk[2][s].v + tb.hb[3] * kk[3][s].v;
   }
 
   __device__ static void term_hess_dirs(const Lds l) {
@@ -1124,16 +1170,20 @@ struct Ocp {
     const Lds l = carve(lbase, ws);
     const OcpConst& pc = *(const OcpConst*)l.pc;
     const int N = pc.N;
-    const int order = DISC ? 1 : pc.order;
-    const double h = pc.dt;
+    const int order = DISC ? 1 : uni(pc.order);
+    const double h = uni(pc.dt);
     const unsigned pinm = FIX_X0 ? (~pc.x0_free_mask) & ((1u << NX) - 1u) : 0u;
-    // tableau entries that can be non-zero for orders 1..4 (modeling.py:1239-1250): a10, a20, a21, a32
-    const double a10 = order >= 2 ? 0.5 : 0.0, a20 = order == 3 ? -1.0 : 0.0, a21 = order == 3 ? 2.0 : (order == 4 ? 0.5 : 0.0),
-                 a32 = order == 4 ? 1.0 : 0.0;
-    const double hb[4] = {DISC ? 1.0 : h * erk_b<0>(order), DISC ? 0.0 : h * erk_b<1>(order), DISC ? 0.0 : h * erk_b<2>(order),
-                          DISC ? 0.0 : h * erk_b<3>(order)};
-    const double* par = (const double*)l.par;
     DTICK0
+    // wave-uniform inputs of every stage, once for the phase and in scalar registers (see sym_tab): step-size products of the
+    // tableau, model parameters [p | u_old], scalings and their reciprocals
+    const SymTab tb = sym_tab<DISC>(order, h);
+    double parv[NPAR], sz[NZ], isz[NX];
+    sym_par(l.par, parv);
+    const double* par = parv;
+#pragma unroll
+    for (int i = 0; i < NZ; ++i) sz[i] = uni(pc.sz[i]);
+#pragma unroll
+    for (int i = 0; i < NX; ++i) isz[i] = uni(rcp_fast(sz[i]));
     double fpart = 0.0;
     OCP_FOR(a, NU) l.grad[N * NZ + NX + a] = 0.0;
     DTICK(7)
@@ -1143,15 +1193,11 @@ struct Ocp {
       const int li = (int)threadIdx.x / LPI;
       const bool act = li < IPP && kbase + li < N;
       const int k = act ? kbase + li : N - 1, g = act ? (int)threadIdx.x - li * LPI : 0, c0 = g * CPL;
-      double zs[NZ], sz[NZ], isz[NX], x[NX], u[NU > 0 ? NU : 1], lamp[NX], X[4][NX], kb[4][NX];
+      double zs[NZ], x[NX], u[NU > 0 ? NU : 1], lamp[NX], X[4][NX], kb[4][NX];
 #pragma unroll
-      for (int i = 0; i < NZ; ++i) {
-        zs[i] = l.Z[k * NZ + i];
-        sz[i] = pc.sz[i];
-      }
+      for (int i = 0; i < NZ; ++i) zs[i] = l.Z[k * NZ + i];
 #pragma unroll
       for (int i = 0; i < NX; ++i) {
-        isz[i] = rcp_fast(sz[i]);
         x[i] = zs[i] * sz[i];
         lamp[i] = l.lam[k * NX + i] * isz[i];
       }
@@ -1198,7 +1244,7 @@ struct Ocp {
       DTICK(5)
       if (!reuse) {  // stage points, slopes, Phi, defect
         double phi[NX];
-        sym_points<M>(order, h, x, u, par, X, phi);
+        sym_points<M>(order, h, tb, x, u, par, X, phi);
         if (act && g == 0) {
 #pragma unroll
           for (int s = 0; s < NX; ++s) l.c[k * NX + s] = l.Z[(k + 1) * NZ + s] - phi[s] * isz[s];
@@ -1215,7 +1261,7 @@ struct Ocp {
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int s = 0; s < NX; ++s) kb[i][s] = hb[i] * lamp[s];
+        for (int s = 0; s < NX; ++s) kb[i][s] = tb.hb[i] * lamp[s];
 #pragma unroll
       for (int j = 3; j >= 1; --j) {
         if (j < order) {
@@ -1231,9 +1277,9 @@ struct Ocp {
           }
 #pragma unroll
           for (int n = 0; n < NX; ++n) {
-            if (j == 3) kb[2][n] += (h * a32) * t[n];
-            if (j == 2) { kb[1][n] += (h * a21) * t[n]; kb[0][n] += (h * a20) * t[n]; }
-            if (j == 1) kb[0][n] += (h * a10) * t[n];
+            if (j == 3) kb[2][n] += tb.ha32 * t[n];
+            if (j == 2) { kb[1][n] += tb.ha21 * t[n]; kb[0][n] += tb.ha20 * t[n]; }
+            if (j == 1) kb[0][n] += tb.ha10 * t[n];
           }
         }
       }
@@ -1263,14 +1309,26 @@ struct Ocp {
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         if (i < order) {
-          if (act) {
+          // Stage 0 works on the unit seeds dX_0 = [I 0]: row r of dW_0^T is e_r, so G[r] += dW_0[:, r]^T v is
+          //   0 + (r >= NX ? v[r] : 0) + sum_a (a == r ? 1 : 0) v[a] = v[r]
+          // and the tangent block need not travel: no store, no barriers, no block read, no products.  Exact, bit for bit, for
+          // finite v: a product with 0 is +-0 and with 1 the factor itself, and v never is -0 (a sum that starts from +0) - the sum
+          // adds zeros to v[r].  A non-finite v[a], a < NX, turns every row of G into NaN in the products (0 inf, 0 NaN): then, for
+          // the whole wave, the stage runs the exchange and the products after all and the NaN spreads exactly as it did
+          // (status -1).  dK_0 and v_0 keep the products with the 0/1 factors: a column of J / H picked with selects costs as much.
+          // (One wave per instance: the barriers of the exchange sit behind a wave-uniform branch.)
+          constexpr bool UNIT = OCP_TPB == 64;
+          const bool unit0 = UNIT && i == 0;
+          if (!unit0) {
+            if (act) {
 #pragma unroll
-            for (int s = 0; s < NX; ++s)
+              for (int s = 0; s < NX; ++s)
 #pragma unroll
-              for (int c = 0; c < CPL; ++c)
-                if (c0 + c < NZ) scr[s * NZ + c0 + c] = dXc[s][c];
+                for (int c = 0; c < CPL; ++c)
+                  if (c0 + c < NZ) scr[s * NZ + c0 + c] = dXc[s][c];
+            }
+            __syncthreads();
           }
-          __syncthreads();
           double dK[NX][CPL], v[NZ][CPL];
           {
             double J[NX * NZ], H[NZ * (NZ + 1) / 2];
@@ -1297,31 +1355,73 @@ struct Ocp {
               }
             }
           }
-          // G[r][col] += dW_i[:, r]^T v = sum_{a < NX} dX_i[a][r] v[a] + (r >= NX ? v[r] : 0)
+          bool redo = false;   // wave-uniform: stage 0 has to run the exchange and the products after all
+          if (unit0) {
+            double chk = 0.0;   // NaN iff a v[a], a < NX, of this lane is not finite
 #pragma unroll
-          for (int r = 0; r < NZ; ++r) {
-            double col_r[NX];
+            for (int a = 0; a < NX; ++a)
 #pragma unroll
-            for (int a = 0; a < NX; ++a) col_r[a] = scr[a * NZ + r];
+              for (int c = 0; c < CPL; ++c) chk += v[a][c] * 0.0;
+            redo = __any((int)(chk != chk)) != 0;
+          }
+          if (!unit0) {
+            // G[r][col] += dW_i[:, r]^T v = sum_{a < NX} dX_i[a][r] v[a] + (r >= NX ? v[r] : 0)
 #pragma unroll
-            for (int c = 0; c < CPL; ++c) {
-              double acc = r >= NX ? v[r][c] : 0.0;
+            for (int r = 0; r < NZ; ++r) {
+              double col_r[NX];
 #pragma unroll
-              for (int a = 0; a < NX; ++a) acc += col_r[a] * v[a][c];
-              G[r][c] += acc;
+              for (int a = 0; a < NX; ++a) col_r[a] = scr[a * NZ + r];
+#pragma unroll
+              for (int c = 0; c < CPL; ++c) {
+                double acc = r >= NX ? v[r][c] : 0.0;
+#pragma unroll
+                for (int a = 0; a < NX; ++a) acc += col_r[a] * v[a][c];
+                G[r][c] += acc;
+              }
             }
+          } else {
+#pragma unroll
+            for (int r = 0; r < NZ; ++r)
+#pragma unroll
+              for (int c = 0; c < CPL; ++c) G[r][c] = v[r][c];
           }
 #pragma unroll
           for (int s = 0; s < NX; ++s)
 #pragma unroll
             for (int c = 0; c < CPL; ++c) {
               const double e = (c0 + c == s) ? 1.0 : 0.0;
-              dPhi[s][c] += hb[i] * dK[s][c];
-              if (i == 0) { dXc[s][c] = e + (h * a10) * dK[s][c]; dX2[s][c] = e + (h * a20) * dK[s][c]; }
-              if (i == 1) dXc[s][c] = dX2[s][c] + (h * a21) * dK[s][c];
-              if (i == 2) dXc[s][c] = e + (h * a32) * dK[s][c];
+              dPhi[s][c] += tb.hb[i] * dK[s][c];
+              if (i == 0) { dXc[s][c] = e + tb.ha10 * dK[s][c]; dX2[s][c] = e + tb.ha20 * dK[s][c]; }
+              if (i == 1) dXc[s][c] = dX2[s][c] + tb.ha21 * dK[s][c];
+              if (i == 2) dXc[s][c] = e + tb.ha32 * dK[s][c];
             }
-          __syncthreads();   // every lane of the interval has read the block before the next stage overwrites it
+          if (!unit0) __syncthreads();   // every lane of the interval has read the block before the next stage overwrites it
+          // A second copy of the G products above (keep the two alike).  The suite can only see that this path ends in status -1
+          // (tests/test_sym_phase_gpu.py): which G entries turn NaN is not observable once the solve has given up.
+          if (redo) {   // (behind the stage's arithmetic: the stage stays one basic block, like the other stages)
+            if (act) {
+#pragma unroll
+              for (int s = 0; s < NX; ++s)
+#pragma unroll
+                for (int c = 0; c < CPL; ++c)
+                  if (c0 + c < NZ) scr[s * NZ + c0 + c] = (c0 + c == s) ? 1.0 : 0.0;
+            }
+            __syncthreads();
+#pragma unroll
+            for (int r = 0; r < NZ; ++r) {
+              double col_r[NX];
+#pragma unroll
+              for (int a = 0; a < NX; ++a) col_r[a] = scr[a * NZ + r];
+#pragma unroll
+              for (int c = 0; c < CPL; ++c) {
+                double acc = r >= NX ? v[r][c] : 0.0;
+#pragma unroll
+                for (int a = 0; a < NX; ++a) acc += col_r[a] * v[a][c];
+                G[r][c] = 0.0 + acc;
+              }
+            }
+            __syncthreads();
+          }
         }
       }
       DTICK(2)
