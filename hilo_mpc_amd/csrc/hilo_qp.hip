@@ -988,7 +988,8 @@ extern "C" int hilo_qp_create(int n, int m, int device, hilo_qp** out) {
   h->big = h->lds_bytes > 160 * 1024;   // e.g. LMPC with nx=2, nu=1 beyond N = 22
   // small dense QPs (the LMPC of BASELINE configuration 1: n = 32, m = 20): factorisations in registers, padded dimensions
   h->fast_np = n <= 32 ? 32 : (n <= 64 ? 64 : 0);
-  h->fast_mp = h->fast_np == 32 ? (m <= 24 ? 24 : (m <= 32 ? 32 : 0)) : (h->fast_np == 64 ? (m <= 48 ? 48 : (m <= 64 ? 64 : 0)) : 0);
+  // (a <64, 64> variant would need 173 KB of LDS: n <= 64 with m > 48 stays on the LDS-column kernel)
+  h->fast_mp = h->fast_np == 32 ? (m <= 24 ? 24 : (m <= 32 ? 32 : 0)) : (h->fast_np == 64 ? (m <= 48 ? 48 : 0) : 0);
   if (!h->fast_mp) h->fast_np = 0;
   {
     const size_t NP = h->fast_np, MP = h->fast_mp;
@@ -1093,7 +1094,6 @@ extern "C" int hilo_qp_solve_pinned(hilo_qp* h, int64_t batch, const double* H, 
     HILO_QP_FAST(32, 24)
     HILO_QP_FAST(32, 32)
     HILO_QP_FAST(64, 48)
-    HILO_QP_FAST(64, 64)
 #undef HILO_QP_FAST
     HILO_HIP_CHECK(hipGetLastError());
     return HILO_OK;
