@@ -613,8 +613,8 @@ extern "C" int hilo_nmpc_solve_tv(hilo_nmpc* h, int64_t batch, const double* x0,
 }
 
 // Developer aid: per-phase shader-clock totals of instance 0 of the next solves
-// (derivatives, errors+barrier update, Riccati, step lengths, line search, update, #factorisations, #trial points);
-// cycles_host[8]
+// (derivatives, errors+barrier update, Riccati, step lengths, line search, update, #factorisations, #trial points, then per launch:
+// setup, finish); cycles_host[PH_COUNT = 10]
 extern "C" int hilo_nmpc_profile(hilo_nmpc* h, int enable, long long* cycles_host) {
   HILO_REQUIRE(h, "hilo_nmpc_profile: NULL handle");
   HILO_HIP_CHECK(hipSetDevice(h->device));

@@ -85,13 +85,15 @@ inline void ocp_default_options(OcpConst& c) {
 }
 
 // ---- block-wide reductions (result broadcast to every lane) ------------------------------------------------
-struct OpSum { __device__ static double id() { return 0.0; } __device__ static double f(double a, double b) { return a + b; } };
+// (NAN_VOTE: the wave-wide reduction decides once per value whether any lane holds a NaN and links the lanes with the plain
+// operation, see wave_reduce)
+struct OpSum { static constexpr bool NAN_VOTE = false; __device__ static double id() { return 0.0; } __device__ static double f(double a, double b) { return a + b; } };
 // NaN-propagating maximum: fmax() silently drops NaN, which would let an error measure pass its tolerance with a NaN
 // multiplier or residual somewhere in the iterate
 __device__ __forceinline__ double nmax(double a, double b) { return (a != a || a > b) ? a : b; }
-struct OpMax { __device__ static double id() { return -INFINITY; } __device__ static double f(double a, double b) { return nmax(a, b); } };
-struct OpMin { __device__ static double id() { return INFINITY; } __device__ static double f(double a, double b) { return fmin(a, b); } };
-struct OpMax2 { __device__ static double id() { return -INFINITY; } __device__ static double f(double a, double b) { return fmax(a, b); } };   // plain maximum
+struct OpMax { static constexpr bool NAN_VOTE = true; __device__ static double id() { return -INFINITY; } __device__ static double f(double a, double b) { return nmax(a, b); } };
+struct OpMin { static constexpr bool NAN_VOTE = false; __device__ static double id() { return INFINITY; } __device__ static double f(double a, double b) { return fmin(a, b); } };
+struct OpMax2 { static constexpr bool NAN_VOTE = false; __device__ static double id() { return -INFINITY; } __device__ static double f(double a, double b) { return fmax(a, b); } };   // plain maximum
 
 // wave-wide reduction without LDS traffic: DPP lane permutes inside each row of 16 (xor 1, xor 2, half-mirror, mirror), then
 // the four row totals through v_readlane (scalar registers -> broadcast for free)
@@ -121,6 +123,11 @@ __device__ __forceinline__ double read_lane(double v, int lane) {
 // placed before the EXEC restore of such a loop's exit block lost the filter size of a constrained variant - see DESIGN.md).
 __device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
 __device__ __forceinline__ bool uni(bool v) { return __builtin_amdgcn_readfirstlane((int)v) != 0; }
+__device__ __forceinline__ int64_t uni(int64_t v) {
+  const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(unsigned long long)v);
+  const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)((unsigned long long)v >> 32));
+  return (int64_t)(((unsigned long long)hi << 32) | lo);
+}
 __device__ __forceinline__ double uni(double v) {
   return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
 }
@@ -150,8 +157,21 @@ __device__ __forceinline__ double rsq_fast(double x) {
 typedef double v4d __attribute__((ext_vector_type(4)));   // accumulator of v_mfma_f64_16x16x4
 struct FTheta { double f, theta, x; };  // objective and constraint violation of a point (x: sum of the caller's `extra` over the lanes)
 
+// The NaN-propagating maximum across a wave: nmax() in every link of the butterfly is two compares, a mask OR and two selects on a
+// 64-bit value where the plain maximum is one instruction (two with the canonicalisation of the permuted operand, whose bits the
+// compiler cannot vouch for).  The NaN property is needed once per reduced value, not once per link: a wave vote on v != v in
+// front of the levels, plain links, and a flagged value comes back as NaN.
+// Zero signs: nmax(+0, -0) = -0 where v_max_f64 gives +0.  Every value reduced this way is a maximum over 0.0 and magnitudes
+// (fabs: dmax, pmax of kkt_pass; cmax, dmax of restore(); zm of the update: multipliers, compared with 1e3) or feeds a strict
+// comparison with tau > 0 only (r_p, r_z of the step lengths): the sign of a zero result reaches neither a stored number nor a decision.
+__device__ __forceinline__ bool wave_any_nan(double v) { return __builtin_amdgcn_ballot_w64(v != v) != 0ull; }
 template <class Op>
 __device__ __forceinline__ double wave_reduce(double v) {
+  if constexpr (Op::NAN_VOTE) {
+    const bool nan = wave_any_nan(v);
+    const double r = wave_reduce<OpMax2>(v);
+    return nan ? __builtin_nan("") : r;
+  }
   v = Op::f(v, dpp_mov<0xB1>(v));   // quad_perm [1,0,3,2]
   v = Op::f(v, dpp_mov<0x4E>(v));   // quad_perm [2,3,0,1]
   v = Op::f(v, dpp_mov<0x141>(v));  // row_half_mirror
@@ -161,13 +181,14 @@ __device__ __forceinline__ double wave_reduce(double v) {
 
 // Several wave-wide reductions at once, level by level: the permutes of all values, then their operations - one reduction
 // alone is a chain of dependent DPP moves and f64 operations (two wait states and the operation's latency per link, nothing else
-// to issue with one wave per SIMD); n chains in lock step fill each other's gaps.  OPS: R_SUM / R_MAX (NaN-propagating) /
-// R_MIN / R_MAX2 (plain) per value; results are wave-uniform (scalar registers).
+// to issue with one wave per SIMD); n chains in lock step fill each other's gaps.  OPS: R_SUM / R_MAX (NaN-propagating: wave vote
+// in front of the levels and plain links, see wave_reduce) / R_MIN / R_MAX2 (plain) per value; results are wave-uniform (scalar
+// registers).
 enum { R_SUM = 0, R_MAX = 1, R_MIN = 2, R_MAX2 = 3 };
 __device__ __forceinline__ double red_apply(int op, double a, double b) {
   switch (op) {
     case R_SUM: return a + b;
-    case R_MAX: return nmax(a, b);
+    case R_MAX: return fmax(a, b);   // (NaN: decided by the vote of WaveReduceN::run)
     case R_MIN: return fmin(a, b);
     default: return fmax(a, b);
   }
@@ -187,6 +208,9 @@ struct WaveReduceN {
   __device__ __forceinline__ static void run(double* v) {
     static_assert(OCP_TPB == 64, "one wave per instance");
     constexpr int ops[n] = {OPS...};
+    bool nan[n];
+#pragma unroll
+    for (int j = 0; j < n; ++j) nan[j] = ops[j] == R_MAX && wave_any_nan(v[j]);
     level<0xB1>(v);
     level<0x4E>(v);
     level<0x141>(v);
@@ -198,7 +222,10 @@ struct WaveReduceN {
       b[j] = red_apply(ops[j], read_lane(v[j], 32), read_lane(v[j], 48));
     }
 #pragma unroll
-    for (int j = 0; j < n; ++j) v[j] = uni(red_apply(ops[j], a[j], b[j]));
+    for (int j = 0; j < n; ++j) {
+      const double r = uni(red_apply(ops[j], a[j], b[j]));
+      v[j] = nan[j] ? __builtin_nan("") : r;
+    }
   }
 };
 
@@ -321,7 +348,11 @@ __device__ long long g_dprof[32];
 #define DTICKR
 #endif
 
-enum OcpPhase { PH_DERIV = 0, PH_ERR, PH_RICCATI, PH_STEP, PH_LS, PH_UPDATE, PH_NRIC, PH_NLS, PH_COUNT };
+// PH_SETUP / PH_FINISH: per LAUNCH, not per iteration - everything in front of the first iteration (constants, parameter row and
+// warm start into LDS, bounds, start point) and the write-back behind the last.  Stored straight to the counters when they are
+// taken: the per-iteration slots live in scalar registers across the whole solve, these two do not.
+enum OcpPhase { PH_DERIV = 0, PH_ERR, PH_RICCATI, PH_STEP, PH_LS, PH_UPDATE, PH_NRIC, PH_NLS, PH_SETUP, PH_FINISH, PH_COUNT };
+constexpr int PH_ITER_COUNT = PH_SETUP;   // the slots ocp_solve_body accumulates over the iterations
 
 template <class PB>
 struct Ocp {
@@ -622,14 +653,19 @@ struct Ocp {
       sym_par(l.par, vpar);
 #pragma unroll
       for (int i = 0; i < NZ; ++i) vsz[i] = pc.sz[i];
+      double r_inv[SYM_INV];   // the stored reciprocals and tableau products (sym_inv): no Newton chains, no products here
+      if constexpr (SYM_INV_LDS) {
 #pragma unroll
-      for (int i = 0; i < NX; ++i) visz[i] = rcp_fast(vsz[i]);
+        for (int i = 0; i < SYM_INV; ++i) r_inv[i] = sym_inv(l)[i];
+      }
+#pragma unroll
+      for (int i = 0; i < NX; ++i) visz[i] = SYM_INV_LDS ? r_inv[i] : rcp_fast(vsz[i]);
       // (the scalings stay in vector registers here, unlike sz / isz of eval_derivs_sym: with uni() the 20 scalar registers
       // more than this function has free come back as SGPR-to-lane spills - chemostat4, order 4: 730 instead of 679 instructions,
       // 13 v_writelane / 37 v_readlane instead of 0 / 24, two scratch accesses, and the kernel's scratch grows by 8 bytes)
       vorder = PB::Model::DISCRETE ? 1 : uni(pc.order);
       vh = uni(pc.dt);
-      vtb = sym_tab<PB::Model::DISCRETE>(vorder, vh);
+      vtb = SYM_INV_LDS ? sym_tab_stored<PB::Model::DISCRETE>(r_inv, vorder, vh) : sym_tab<PB::Model::DISCRETE>(vorder, vh);
     }
     OCP_FOR(k, (N) + 1) {
       double x[NX], u[NU > 0 ? NU : 1];
@@ -1109,6 +1145,40 @@ struct Ocp {
                   {uni(DISC ? 1.0 : h * erk_b<0>(order)), uni(DISC ? 0.0 : h * erk_b<1>(order)), uni(DISC ? 0.0 : h * erk_b<2>(order)),
                    uni(DISC ? 0.0 : h * erk_b<3>(order))}};
   }
+  // What is the same for the whole SOLVE is formed once, by the load section, and kept in LDS: the reciprocal scalings
+  // [NX] (rcp_fast of pc.sz, the value every phase formed for itself before) and the eight tableau products of sym_tab.  A phase
+  // requests them, the parameters and the scalings in one batch of LDS reads, waits once and makes them uniform: read, wait,
+  // v_readfirstlane trip after trip and four Newton chains in a row cost the head of the derivative phase 1.4 k clocks per call.
+  // They live in the reduction scratch: with one wave per instance block_reduce() never touches it (wave_reduce keeps to registers).
+  // Its 16 doubles hold them for models of up to 8 states (SYM_INV_LDS); a wider model (run-time compiled user models go up to
+  // OCP_MAXNX = 12) or more than one wave per instance forms them in the phase, as before.
+  static constexpr int SYM_INV = NX + 8;
+  static constexpr bool SYM_INV_LDS = OCP_TPB == 64 && SYM_INV <= 16;
+  __device__ __forceinline__ static lds_double* sym_inv(const Lds l) {
+    static_assert(SYM_INV_LDS, "the solve-invariant values of SYM policies live in the reduction scratch");
+    return l.red;
+  }
+  template <bool DISC>
+  __device__ __forceinline__ static void sym_inv_store(const Lds l) {   // (load section, behind the barrier that publishes `pc`)
+    const OcpConst& pc = *(const OcpConst*)l.pc;
+    lds_double* inv = sym_inv(l);
+    const SymTab tb = sym_tab<DISC>(DISC ? 1 : uni(pc.order), uni(pc.dt));
+    const int t = threadIdx.x;
+    if (t < NX) inv[t] = rcp_fast(pc.sz[t]);
+    if (t == 0) {
+      inv[NX + 0] = tb.ha10; inv[NX + 1] = tb.ha20; inv[NX + 2] = tb.ha21; inv[NX + 3] = tb.ha32;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) inv[NX + 4 + j] = tb.hb[j];
+    }
+  }
+  // the tableau products of a phase: from the stored ones (r: SYM_INV values already requested from sym_inv); a discrete model's
+  // are compile-time constants and stay that
+  template <bool DISC>
+  __device__ __forceinline__ static SymTab sym_tab_stored(const double* r, int order, double h) {
+    if constexpr (DISC) return sym_tab<true>(order, h);
+    return SymTab{uni(r[NX + 0]), uni(r[NX + 1]), uni(r[NX + 2]), uni(r[NX + 3]),
+                  {uni(r[NX + 4]), uni(r[NX + 5]), uni(r[NX + 6]), uni(r[NX + 7])}};
+  }
   template <class LP>
   __device__ __forceinline__ static void sym_par(LP lpar, double* parv) {
 #pragma unroll
@@ -1176,14 +1246,28 @@ struct Ocp {
     DTICK0
     // wave-uniform inputs of every stage, once for the phase and in scalar registers (see sym_tab): step-size products of the
     // tableau, model parameters [p | u_old], scalings and their reciprocals
-    const SymTab tb = sym_tab<DISC>(order, h);
+    // (one batch: every LDS read of the head is requested before the first value is made uniform - see sym_inv)
     double parv[NPAR], sz[NZ], isz[NX];
-    sym_par(l.par, parv);
+    double r_inv[SYM_INV], r_par[NPAR], r_sz[NZ];
+    {
+      if constexpr (SYM_INV_LDS) {
+        lds_double* inv = sym_inv(l);
+#pragma unroll
+        for (int i = 0; i < SYM_INV; ++i) r_inv[i] = inv[i];
+      }
+#pragma unroll
+      for (int i = 0; i < NPAR; ++i) r_par[i] = i < PB::NPAR ? l.par[i < PB::NPAR ? i : 0] : 0.0;
+#pragma unroll
+      for (int i = 0; i < NZ; ++i) r_sz[i] = pc.sz[i];
+    }
+    const SymTab tb = SYM_INV_LDS ? sym_tab_stored<DISC>(r_inv, order, h) : sym_tab<DISC>(order, h);
+#pragma unroll
+    for (int i = 0; i < NPAR; ++i) parv[i] = i < PB::NPAR ? uni(r_par[i]) : 0.0;
+#pragma unroll
+    for (int i = 0; i < NZ; ++i) sz[i] = uni(r_sz[i]);
+#pragma unroll
+    for (int i = 0; i < NX; ++i) isz[i] = SYM_INV_LDS ? uni(r_inv[i]) : uni(rcp_fast(sz[i]));
     const double* par = parv;
-#pragma unroll
-    for (int i = 0; i < NZ; ++i) sz[i] = uni(pc.sz[i]);
-#pragma unroll
-    for (int i = 0; i < NX; ++i) isz[i] = uni(rcp_fast(sz[i]));
     double fpart = 0.0;
     OCP_FOR(a, NU) l.grad[N * NZ + NX + a] = 0.0;
     DTICK(7)
@@ -3197,6 +3281,172 @@ struct Ocp {
     }
     return 1;
   }
+  // ---- the load section of a solve: problem constants, the instance's parameter row and stage data into LDS, then the start
+  // point (warm start, x_0 pinned to the measurement, bounds of the call, push into the interior).  A called phase like the four
+  // large ones: its few hundred instructions of address arithmetic run once per launch and share no live range with the iteration.
+  // Every global read of it that does not need a problem constant from LDS is REQUESTED first - the constants themselves, the
+  // instance's parameter row and, for the first two slots a lane owns, the instance's rows (x0, the start vector, the bounds of
+  // this call) - and the section waits once, in front of the stores to LDS.  One wave per SIMD hides no latency: read, wait,
+  // store trip after trip cost one round trip to L2 (or further: rows the previous step's launch wrote) per trip, five for the
+  // constants of the tracking policy, and the slot loop could not ask for its rows before the constants that address them had
+  // come back through LDS.  The few integers those addresses need are wave-uniform and come straight from `pcg` (the compiler reads
+  // them with vector loads and makes them uniform: the horizon is waited for with the constants' loads in flight behind it).
+  // All lanes request from a valid address (clamped index, selects instead of branches) and the result is predicated.
+  __device__ OCP_PHASE static void load_instance(lds_double* lds_raw_in, double* ws_in, const OcpConst* pcg_in, int64_t b_in,
+                                                 const double* x0_in, const double* par_in, int64_t par_stride_in,
+                                                 const double* sdata_in, int64_t sd_stride_in, const double* vb_in, int v_prefix_in,
+                                                 const double* par2_in, int npar1_in, const double* lbx_in, const double* ubx_in,
+                                                 int64_t bx_stride_in) {
+    using S = Ocp<PB>;
+    constexpr int NTAIL = NX - NXV - NH;
+    // (arguments of a called function arrive in vector registers and as generic pointers: back to scalar registers, see uni(), and
+    // to the global address space - flat loads otherwise)
+    using gbl_const = const __attribute__((address_space(1))) OcpConst;
+    lds_double* const lds_raw = uni(lds_raw_in);
+    double* const wsb = uni(ws_in);
+    gbl_const* const pcg = (gbl_const*)uni(pcg_in);
+    const int64_t b = uni(b_in), par_stride = uni(par_stride_in), sd_stride = uni(sd_stride_in), bx_stride = uni(bx_stride_in);
+    gbl_cdouble *const x0 = (gbl_cdouble*)uni(x0_in), *const par = (gbl_cdouble*)uni(par_in), *const sdata = (gbl_cdouble*)uni(sdata_in),
+                *const vb = (gbl_cdouble*)uni(vb_in), *const par2 = (gbl_cdouble*)uni(par2_in), *const lbx = (gbl_cdouble*)uni(lbx_in),
+                *const ubx = (gbl_cdouble*)uni(ubx_in);
+    const int v_prefix = uni(v_prefix_in), npar1 = uni(npar1_in);
+    const int t = threadIdx.x;
+    const int N = uni(pcg->N);
+    const Lds l = carve(lds_raw, wsb, N);
+    constexpr int CT = (S::NCONST + OCP_TPB - 1) / OCP_TPB, PT = (PB::NPAR + OCP_TPB - 1) / OCP_TPB;
+    gbl_cdouble* const csrc = reinterpret_cast<gbl_cdouble*>(pcg);
+    double cbuf[CT], pbuf[PT > 0 ? PT : 1];
+#pragma unroll
+    for (int j = 0; j < CT; ++j) {
+      const int i = j * OCP_TPB + t;
+      cbuf[j] = csrc[i < S::NCONST ? i : 0];
+    }
+    {
+      const int n1 = par2 || npar1 > 0 ? npar1 : PB::NPAR;   // default: the whole row from `par`
+      // (two wave-uniform branches and an index select: a per-lane choice between the two base pointers compiles to an if / else
+      // region of its own under the run-time compiler)
+      const bool has1 = n1 > 0, has2 = par2 != nullptr && n1 < PB::NPAR;
+#pragma unroll
+      for (int j = 0; j < PT; ++j) {
+        const int i = j * OCP_TPB + t;
+        const bool p1 = i < PB::NPAR && i < n1, p2 = i < PB::NPAR && !p1 && has2;
+        double v1 = 0.0, v2 = 0.0;
+        if (has1) v1 = par[b * par_stride + (p1 ? i : 0)];
+        if (has2) v2 = par2[b * (int64_t)(PB::NPAR - n1) + (p2 ? i - n1 : 0)];
+        pbuf[j] = p1 ? v1 : (p2 ? v2 : 0.0);
+      }
+    }
+    const int SL = (N + 1) * NZ;
+    const int flags_g = uni(pcg->flags), tail_g = uni(pcg->tail_off), Ncv = NH > 0 ? uni(pcg->Nc) : N;
+    FreeTest is_free_g;   // (== free_test(), from the constants in global memory)
+    is_free_g.pinm = uni((int)(FIX_X0 ? (~pcg->x0_free_mask) & ((1u << NX) - 1u) : 0u));
+    is_free_g.N = N;
+    is_free_g.Nc = NH > 0 ? Ncv : 0;
+    // reference layout [x (NXV per stage) | u | shared tail]; the tail is carried as constant states (same value in every stage)
+    const int toff = tail_g > 0 ? tail_g : (N + 1) * NXV + Ncv * NU;
+    struct SlotIn { double raw, lo, up; bool pin, bx; };   // what a slot reads from global memory: start value or x0 entry, bounds of the call
+    auto slot_request = [&](int e_in) {
+      const int e = e_in < SL ? e_in : 0;
+      const int k = e / NZ, i = e - k * NZ;
+      SlotIn in;
+      in.pin = k == 0 && i < NXV && ((is_free_g.pinm >> i) & 1u);   // == S::x0_pinned
+      // with a control horizon Nc < N the reference holds Nc input blocks; the held copy of stage k is the input of stage
+      // min(k - 1, Nc - 1) (zero at stage 0, where it is pinned and never read)
+      int src;
+      bool zero = false;
+      if (i < NXV) src = k * NXV + i;
+      else if (i < NXV + NTAIL) src = toff + (i - NXV);
+      else if (i < NX) { zero = k == 0; src = (N + 1) * NXV + ((k - 1 < Ncv ? k - 1 : Ncv - 1)) * NU + (i - NXV - NTAIL); }
+      else { zero = k >= Ncv; src = (N + 1) * NXV + k * NU + (i - NX); }
+      gbl_cdouble* p = in.pin ? x0 + (b * S::NX0 + i) : vb + (zero ? 0 : src);
+      const double r = *p;
+      in.raw = zero ? 0.0 : r;
+      in.lo = 0.0; in.up = 0.0; in.bx = false;
+      if (lbx) {   // bounds of this call (the box of a free x_0 stays its own): the slot's entry of the reference's lbx / ubx (same index as in v)
+        int bs = -1;
+        if (i < NXV) bs = k * NXV + i;
+        else if (i < NXV + NTAIL) bs = k == 0 ? toff + (i - NXV) : -1;
+        else if (i >= NX && k < Ncv) bs = (N + 1) * NXV + k * NU + (i - NX);
+        in.bx = is_free_g(k, i) && !(k == 0 && (flags_g & 2) && i < S::NX0) && bs >= 0;
+        const int64_t off = b * bx_stride + v_prefix + (in.bx ? bs : 0);
+        in.lo = lbx[off];
+        in.up = ubx[off];
+      }
+      return in;
+    };
+    constexpr int UPRE = 2;   // slots per lane requested in front of the barrier (the tracking benchmark has 126 slots: all of them)
+    SlotIn pre[UPRE];
+#pragma unroll
+    for (int u = 0; u < UPRE; ++u) pre[u] = slot_request(u * OCP_TPB + t);
+    {  // problem constants into LDS: every later access is an LDS read instead of a global load
+#pragma unroll
+      for (int j = 0; j < CT; ++j) {
+        const int i = j * OCP_TPB + t;
+        if (i < S::NCONST) lds_raw[i] = cbuf[j];
+      }
+#pragma unroll
+      for (int j = 0; j < PT; ++j) {
+        const int i = j * OCP_TPB + t;
+        if (i < PB::NPAR) l.par[i] = pbuf[j];
+      }
+    }
+    if constexpr (PB::NSD > 0)
+      OCP_FOR(i, (N + 1) * PB::NSD) l.sd[i] = sdata[b * sd_stride + i];
+    if constexpr (S::COOP) {   // the learned term's table into LDS: every kernel-sum term is an LDS read instead of an L2 round trip
+      gbl_cdouble* gsrc = (gbl_cdouble*)pcg->ext;
+      const int nt = GP2_HDR + 3 * (int)gsrc[0];
+      OCP_FOR(i, nt) l.ext[S::NEXT_SCR + i] = gsrc[i];
+    }
+    __syncthreads();
+    const OcpConst& pc = *(const OcpConst*)l.pc;
+    if constexpr (SYM && SYM_INV_LDS) sym_inv_store<PB::Model::DISCRETE>(l);
+
+    // ---- warm start in the [x-block | u-block] layout; x_0 pinned to the measurement (mpc.py:801-802).  The arithmetic of a slot is
+    // what it always was (IEEE division of x0 by its scaling, bound relaxation, push into the interior); only its operands are
+    // already on their way when the barrier is passed ----
+    auto slot_store = [&](int e, const SlotIn& in) {
+      const int k = e / NZ, i = e - k * NZ;
+      double v = in.raw;
+      if (in.pin) v = in.raw / pc.sz[i];
+      const bool fr = is_free_g(k, i);
+      double lb = fr ? S::lb_of(pc, k, i) : -INFINITY, ub = fr ? S::ub_of(pc, k, i) : INFINITY;
+      if (in.bx) {
+        const double lo = in.lo, up = in.up;
+        lb = lo > -INFINITY ? lo - pc.bound_relax * fmax(1.0, fabs(lo)) : lo;
+        ub = up < INFINITY ? up + pc.bound_relax * fmax(1.0, fabs(up)) : up;
+      }
+      l.lbA[e] = lb;
+      l.ubA[e] = ub;
+      if (fr) {  // IPOPT start: push into the interior (W&B sec. 3.6)
+        const bool hl = lb > -INFINITY, hu = ub < INFINITY;
+        if (hl) {
+          double pl = pc.bound_push * fmax(1.0, fabs(lb));
+          if (hu) pl = fmin(pl, pc.bound_frac * (ub - lb));
+          v = fmax(v, lb + pl);
+        }
+        if (hu) {
+          double pu = pc.bound_push * fmax(1.0, fabs(ub));
+          if (hl) pu = fmin(pu, pc.bound_frac * (ub - lb));
+          v = fmin(v, ub - pu);
+        }
+        l.zL[e] = hl ? 1.0 : 0.0;
+        l.zU[e] = hu ? 1.0 : 0.0;
+      } else {
+        l.zL[e] = 0.0;
+        l.zU[e] = 0.0;
+      }
+      l.Z[e] = v;
+      l.D[e] = 0.0;
+    };
+#pragma unroll
+    for (int u = 0; u < UPRE; ++u)
+      if (const int e = u * OCP_TPB + t; e < SL) slot_store(e, pre[u]);
+    for (int e_base = UPRE * OCP_TPB; e_base < SL; e_base += OCP_TPB) {   // longer horizons: the remaining trips, request and use
+      const int e = e_base + t;
+      const SlotIn in = slot_request(e);
+      if (e < SL) slot_store(e, in);
+    }
+  }
 };
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -3224,83 +3474,15 @@ __device__ __forceinline__ void ocp_solve_body(lds_double* lds_raw, const OcpCon
   const int N = pcg->N;
   double* const wsb = ws ? ws + (ws_slot >= 0 ? ws_slot : b) * (int64_t)S::ws_doubles(N) : nullptr;
   typename S::Lds l = S::carve(lds_raw, wsb, N);
-  {  // problem constants into LDS: every later access is an LDS read instead of a global load
-    const double* src = reinterpret_cast<const double*>(pcg);
-    lds_double* dst = lds_raw;
-    OCP_FOR(i, S::NCONST) dst[i] = src[i];
-  }
-  {
-    const int n1 = ex.par2 || ex.npar1 > 0 ? ex.npar1 : PB::NPAR;   // default: the whole row from `par`
-    OCP_FOR(i, PB::NPAR) {
-      double v = 0.0;
-      if (i < n1) v = par[b * par_stride + i];
-      else if (ex.par2) v = ex.par2[b * (int64_t)(PB::NPAR - n1) + (i - n1)];
-      l.par[i] = v;
-    }
-  }
-  if constexpr (PB::NSD > 0)
-    OCP_FOR(i, (N + 1) * PB::NSD) l.sd[i] = sdata[b * sd_stride + i];
-  if constexpr (S::COOP) {   // the learned term's table into LDS: every kernel-sum term is an LDS read instead of an L2 round trip
-    const double* gsrc = pcg->ext;
-    const int nt = GP2_HDR + 3 * (int)gsrc[0];
-    OCP_FOR(i, nt) l.ext[S::NEXT_SCR + i] = gsrc[i];
-  }
-  __syncthreads();
-  const OcpConst& pc = *(const OcpConst*)l.pc;
-  const int SL = (N + 1) * NZ;
-  long long tprof[PH_COUNT] = {0, 0, 0, 0, 0, 0, 0, 0};
   long long tlast = prof ? clock64() : 0;
+  // ---- load: constants, parameter row, stage data and the start point into LDS (load_instance) ----
+  S::load_instance(lds_raw, wsb, pcg, b, x0, par, par_stride, sdata, sd_stride, v0 + b * v0_stride + v0_prefix, v_prefix, ex.par2,
+                   ex.npar1, ex.lbx, ex.ubx, ex.bx_stride);
+  const int SL = (N + 1) * NZ;
+  const OcpConst& pc = *(const OcpConst*)l.pc;
+  long long tprof[PH_ITER_COUNT] = {0, 0, 0, 0, 0, 0, 0, 0};
 #define OCP_TICK(ph) if (prof) { const long long tn = clock64(); tprof[ph] += tn - tlast; tlast = tn; }
 
-  // ---- load: warm start in the [x-block | u-block] layout; x_0 pinned to the measurement (mpc.py:801-802) ----
-  const double* vb = v0 + b * v0_stride + v0_prefix;
-  OCP_FOR(e, SL) {
-    const int k = e / NZ, i = e - k * NZ;
-    double v;
-    // reference layout [x (NXV per stage) | u | shared tail]; the tail is carried as constant states (same value in every stage)
-    // with a control horizon Nc < N the reference holds Nc input blocks; the held copy of stage k is the input of stage
-    // min(k - 1, Nc - 1) (zero at stage 0, where it is pinned and never read)
-    const int Ncv = NH > 0 ? pc.Nc : N;
-    if (i < NXV) v = (k == 0 && S::x0_pinned(pc, i)) ? x0[b * S::NX0 + i] / pc.sz[i] : vb[k * NXV + i];
-    else if (i < NXV + NTAIL) v = vb[(pc.tail_off > 0 ? pc.tail_off : (N + 1) * NXV + Ncv * NU) + (i - NXV)];
-    else if (i < NX) v = k == 0 ? 0.0 : vb[(N + 1) * NXV + ((k - 1 < Ncv ? k - 1 : Ncv - 1)) * NU + (i - NXV - NTAIL)];
-    else v = (k < Ncv) ? vb[(N + 1) * NXV + k * NU + (i - NX)] : 0.0;
-    const bool fr = S::is_free(pc, k, i);
-    double lb = fr ? S::lb_of(pc, k, i) : -INFINITY, ub = fr ? S::ub_of(pc, k, i) : INFINITY;
-    if (ex.lbx && fr && !(k == 0 && (pc.flags & 2) && i < S::NX0)) {   // bounds of this call (the box of a free x_0 stays its own): the slot's entry of the reference's lbx / ubx (same index as in v)
-      int src = -1;
-      if (i < NXV) src = k * NXV + i;
-      else if (i < NXV + NTAIL) { if (k == 0) src = (pc.tail_off > 0 ? pc.tail_off : (N + 1) * NXV + Ncv * NU) + (i - NXV); }
-      else if (i >= NX && k < Ncv) src = (N + 1) * NXV + k * NU + (i - NX);
-      if (src >= 0) {
-        const double lo = ex.lbx[b * ex.bx_stride + v_prefix + src], up = ex.ubx[b * ex.bx_stride + v_prefix + src];
-        lb = lo > -INFINITY ? lo - pc.bound_relax * fmax(1.0, fabs(lo)) : lo;
-        ub = up < INFINITY ? up + pc.bound_relax * fmax(1.0, fabs(up)) : up;
-      }
-    }
-    l.lbA[e] = lb;
-    l.ubA[e] = ub;
-    if (fr) {  // IPOPT start: push into the interior (W&B sec. 3.6)
-      const bool hl = lb > -INFINITY, hu = ub < INFINITY;
-      if (hl) {
-        double pl = pc.bound_push * fmax(1.0, fabs(lb));
-        if (hu) pl = fmin(pl, pc.bound_frac * (ub - lb));
-        v = fmax(v, lb + pl);
-      }
-      if (hu) {
-        double pu = pc.bound_push * fmax(1.0, fabs(ub));
-        if (hl) pu = fmin(pu, pc.bound_frac * (ub - lb));
-        v = fmin(v, ub - pu);
-      }
-      l.zL[e] = hl ? 1.0 : 0.0;
-      l.zU[e] = hu ? 1.0 : 0.0;
-    } else {
-      l.zL[e] = 0.0;
-      l.zU[e] = 0.0;
-    }
-    l.Z[e] = v;
-    l.D[e] = 0.0;
-  }
   OCP_FOR(e, N * NX) l.lam[e] = 0.0;
   if constexpr (NC > 0) {
     OCP_FOR(e, N * NC) {
@@ -3352,6 +3534,11 @@ __device__ __forceinline__ void ocp_solve_body(lds_double* lds_raw, const OcpCon
   const double nb_const = S::count_bounds(l);
   bool pts_ok = false;      // SYM policies: the iterate is the trial point the line search evaluated last (stage points, defects, f)
   double f_trial = 0.0;
+  if (prof) {
+    const long long tn = clock64();
+    if (b == 0 && t == 0) prof[PH_SETUP] = tn - tlast;
+    tlast = tn;
+  }
   for (it = 0;; ++it) {
     if constexpr (S::SYM) {
       if (pts_ok) {
@@ -3734,6 +3921,7 @@ __device__ __forceinline__ void ocp_solve_body(lds_double* lds_raw, const OcpCon
   }
 
   // ---- write back ([x-block | u-block] after the prefix) ----
+  if (prof) tlast = clock64();   // (the error pass that ended the loop belongs to no slot)
   const int Ncw = NH > 0 ? pc.Nc : N;
   double* vo = v_opt + b * (int64_t)(v_prefix + (N + 1) * NXV + Ncw * NU + NTAIL) + v_prefix;
   double* const vo2 = ex.v_copy ? ex.v_copy + (vo - v_opt) : nullptr;
@@ -3825,8 +4013,10 @@ __device__ __forceinline__ void ocp_solve_body(lds_double* lds_raw, const OcpCon
     status[b] = st;
     iters[b] = it;
     if (kkt) kkt[b] = E0;
-    if (prof && b == 0)
-      for (int q = 0; q < PH_COUNT; ++q) prof[q] = tprof[q];
+    if (prof && b == 0) {
+      for (int q = 0; q < PH_ITER_COUNT; ++q) prof[q] = tprof[q];
+      prof[PH_FINISH] = clock64() - tlast;
+    }
   }
 #undef OCP_TICK
 }

@@ -1649,11 +1649,18 @@ class NMPC:
         """Developer aid (hilo_nmpc_profile): shader-clock cycles instance 0 spent per solver phase in the launches
         since the last call.  Returns a dict or None when collection was just switched on."""
         names = ['derivatives', 'errors', 'riccati', 'step', 'line_search', 'update', 'n_factorizations', 'n_trial_points']
-        buf = (C.c_longlong * 8)()
+        buf = (C.c_longlong * 10)()
         had = getattr(self, '_prof_on', False)
         _lib.check(_lib.lib().hilo_nmpc_profile(self._handle, int(bool(enable)), buf if had else None))
         self._prof_on = bool(enable)
-        return dict(zip(names, list(buf))) if had else None
+        self._prof_ends = dict(setup=buf[8], finish=buf[9]) if had else None
+        return dict(zip(names, list(buf)[:8])) if had else None
+
+    def phase_profile_ends(self):
+        """The two per-LAUNCH slots that came with the last `phase_profile()` read-out: shader-clock cycles of instance 0 in front of
+        the first iteration ('setup': constants, parameter row and warm start into LDS, bounds, start point) and behind the last
+        ('finish': the write-back) of the most recent launch.  None before the first read-out."""
+        return getattr(self, '_prof_ends', None)
 
     @property
     def keep_full_solution(self):

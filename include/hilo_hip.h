@@ -534,8 +534,9 @@ int hilo_nmpc_solve_tv(hilo_nmpc* h, int64_t batch, const double* x0, const doub
                        const double* v0, const double* u_old, double* v_opt, double* f_opt, double* lam_g, double* u0,
                        int32_t* status, int32_t* iters, double* kkt, void* stream);
 /* developer aid: per-phase shader-clock totals of instance 0 (derivatives, errors, Riccati, step, line search,
-   update, number of factorisations, number of line-search trial points); enable != 0 starts collecting,
-   cycles_host[8] (may be NULL) receives the last launch's counters */
+   update, number of factorisations, number of line-search trial points, then the two per-launch slots: setup =
+   everything in front of the first iteration, finish = the write-back); enable != 0 starts collecting,
+   cycles_host[10] (may be NULL) receives the last launch's counters */
 int hilo_nmpc_profile(hilo_nmpc* h, int enable, long long* cycles_host);
 /* x+ = Phi(x, u, p) with the controller's own shooting map: closed-loop harness (control_loop.py:343-396) */
 int hilo_nmpc_plant_step(hilo_nmpc* h, int64_t batch, const double* x, const double* u, const double* p,

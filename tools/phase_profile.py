@@ -22,4 +22,5 @@ it = int(nmpc._nlp_solution['iter_count'][0])
 its = nmpc._nlp_solution['iter_count'].double()
 print(cfg, 'B', B, 'launch ms', round(dt * 1e3, 3), 'iters inst0', it, 'mean', round(float(its.mean()), 2), 'max', float(its.max()),
       {k: (v if k.startswith('n_') else round(v / max(it, 1))) for k, v in pr.items()},
-      'sum', round(sum(v for k, v in pr.items() if not k.startswith('n_')) / max(it, 1)))
+      'sum', round(sum(v for k, v in pr.items() if not k.startswith('n_')) / max(it, 1)),
+      'per launch', nmpc.phase_profile_ends())
