@@ -229,6 +229,32 @@ struct NmpcTrack {
     for (int j = 0; j < NX; ++j) g += (pc.cost[O_WN + i * NX + j] + pc.cost[O_WN + j * NX + i]) * (x[j] - pc.cost[O_XREFN + j]);
     return g;
   }
+  // Gradient entries gN[c] of the terminal cost for the columns c0, c0 + 1, .. (beyond NX: the last one again) at the point x: the
+  // rows and columns of WN and the reference, all requested before the first use and without a branch, for a caller that puts them
+  // next to the reads of cost_cols and keeps only its store under a condition.  Same products, same order of the sum as term_grad.
+  template <int CPL>
+  __device__ __forceinline__ static void term_cols(const OcpConst& pc, int c0, const double* x, double* gN) {
+    double wr[NX][CPL], wc[NX][CPL], xr[NX];
+    int col[CPL];
+#pragma unroll
+    for (int c = 0; c < CPL; ++c) col[c] = c0 + c < NX ? c0 + c : NX - 1;
+#pragma unroll
+    for (int j = 0; j < NX; ++j) {
+      xr[j] = pc.cost[O_XREFN + j];
+#pragma unroll
+      for (int c = 0; c < CPL; ++c) {
+        wr[j][c] = pc.cost[O_WN + col[c] * NX + j];
+        wc[j][c] = pc.cost[O_WN + j * NX + col[c]];
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < CPL; ++c) {
+      double g = 0.0;
+#pragma unroll
+      for (int j = 0; j < NX; ++j) g += (wr[j][c] + wc[j][c]) * (x[j] - xr[j]);
+      gN[c] = g;
+    }
+  }
   __device__ __forceinline__ static double term_hess(const OcpConst& pc, int i, int j) {
     return pc.cost[O_WN + i * NX + j] + pc.cost[O_WN + j * NX + i];
   }

@@ -37,6 +37,12 @@ constexpr int OCP_MAXNC = 16;  // nonlinear inequality rows per stage (stage row
 #else
 #define OCP_PHASE __attribute__((noinline))
 #endif
+// developer knob, all on in the product: the seams of the iteration that can be built out one by one to measure them (bit 0: cost
+// section of eval_derivs_sym without conditional reads, bit 1: defects copied by the update)
+#ifndef HILO_OCP_SEAMS
+#define HILO_OCP_SEAMS 3
+#endif
+constexpr int OCP_SEAMS = HILO_OCP_SEAMS;
 constexpr int OCP_TPB = HILO_OCP_TPB;  // threads per instance (one or more waves)
 constexpr int OCP_NCOST = 2 * OCP_MAXNZ * OCP_MAXNZ + 4 * OCP_MAXNZ + 64;
 
@@ -1242,13 +1248,14 @@ struct Ocp {
     const int N = pc.N;
     const int order = DISC ? 1 : uni(pc.order);
     const double h = uni(pc.dt);
-    const unsigned pinm = FIX_X0 ? (~pc.x0_free_mask) & ((1u << NX) - 1u) : 0u;
     DTICK0
     // wave-uniform inputs of every stage, once for the phase and in scalar registers (see sym_tab): step-size products of the
-    // tableau, model parameters [p | u_old], scalings and their reciprocals
+    // tableau, model parameters [p | u_old], scalings and their reciprocals, the constants of the free-slot test (free_test)
     // (one batch: every LDS read of the head is requested before the first value is made uniform - see sym_inv)
     double parv[NPAR], sz[NZ], isz[NX];
     double r_inv[SYM_INV], r_par[NPAR], r_sz[NZ];
+    const unsigned r_fm = pc.x0_free_mask;
+    const int r_nc = NH > 0 ? pc.Nc : 0;
     {
       if constexpr (SYM_INV_LDS) {
         lds_double* inv = sym_inv(l);
@@ -1267,6 +1274,11 @@ struct Ocp {
     for (int i = 0; i < NZ; ++i) sz[i] = uni(r_sz[i]);
 #pragma unroll
     for (int i = 0; i < NX; ++i) isz[i] = SYM_INV_LDS ? uni(r_inv[i]) : uni(rcp_fast(sz[i]));
+    FreeTest free_at;   // (== free_test(pc): nothing below reads `pc` inside a conditional block)
+    free_at.pinm = uni((int)(FIX_X0 ? (~r_fm) & ((1u << NX) - 1u) : 0u));
+    free_at.N = uni(N);
+    free_at.Nc = uni(r_nc);
+    const unsigned pinm = free_at.pinm;   // pinned slots of x_0 (bit i)
     const double* par = parv;
     double fpart = 0.0;
     OCP_FOR(a, NU) l.grad[N * NZ + NX + a] = 0.0;
@@ -1295,34 +1307,58 @@ struct Ocp {
         double xN[NX];
 #pragma unroll
         for (int i = 0; i < NX; ++i) xN[i] = l.Z[N * NZ + i];
-        if constexpr (pb_symtab<PB>::value) {
+        // gradient entries of this lane's columns at every lane, the terminal cost's among them (term_cols next to the reads of
+        // cost_cols: one batch of LDS reads, no branch); only the stores are predicated - a conditional block per column with
+        // reads of its own is a chain of dependent LDS round trips that every wave walks (each holds lanes of interval N - 1)
+        if constexpr (OCP_SEAMS & 1) {
+        double gc[CPL], gN[CPL];
+        if constexpr (pb_symtab<PB>::value) PB::template cost_cols<CPL>(pc, par, k, c0, zs, gc, ch);
+        else {
+#pragma unroll
+          for (int c = 0; c < CPL; ++c) {
+            const int col = c0 + c < NZ ? c0 + c : NZ - 1;
+            gc[c] = PB::cost_grad(pc, par, sd_of(l, k), k, col, zs);
+#pragma unroll
+            for (int r = 0; r < NZ; ++r) ch[r][c] = (c0 + c < NZ && r >= c0 + c) ? PB::cost_hess(pc, k, r, c0 + c) : 0.0;
+          }
+        }
+        PB::template term_cols<CPL>(pc, c0, xN, gN);
+        if (act && g == 0 && !reuse) {
+          fpart += PB::stage_cost(pc, par, sd_of(l, k), k, zs, zs + NX);
+          if (k == N - 1) fpart += PB::term_cost(pc, par, sd_of(l, N), xN);
+        }
+#pragma unroll
+        for (int c = 0; c < CPL; ++c) {
+          gc[c] = free_at(k, c0 + c) ? gc[c] : 0.0;
+          // (the values are final here: left alone the compiler sinks each sum into the conditional block of its store)
+          asm volatile("" : "+v"(gc[c]), "+v"(gN[c]));
+        }
+#pragma unroll
+        for (int c = 0; c < CPL; ++c) {
+          const int col = c0 + c;
+          if (act && col < NZ) l.grad[k * NZ + col] = gc[c];
+          if (act && col < NX && k == free_at.N - 1) l.grad[free_at.N * NZ + col] = gN[c];
+        }
+        } else {   // (developer builds: the conditional block per column, for comparison)
           double gc[CPL];
-          PB::template cost_cols<CPL>(pc, par, k, c0, zs, gc, ch);
+          if constexpr (pb_symtab<PB>::value) PB::template cost_cols<CPL>(pc, par, k, c0, zs, gc, ch);
           if (act) {
             if (g == 0 && !reuse) fpart += PB::stage_cost(pc, par, sd_of(l, k), k, zs, zs + NX);
             if (g == 0 && k == N - 1 && !reuse) fpart += PB::term_cost(pc, par, sd_of(l, N), xN);
 #pragma unroll
             for (int c = 0; c < CPL; ++c) {
               const int col = c0 + c;
+              if constexpr (!pb_symtab<PB>::value) gc[c] = col < NZ ? PB::cost_grad(pc, par, sd_of(l, k), k, col, zs) : 0.0;
               if (col < NZ) l.grad[k * NZ + col] = is_free(pc, k, col) ? gc[c] : 0.0;
               if (col < NX && k == N - 1) l.grad[N * NZ + col] = PB::term_grad(pc, col, xN);
             }
           }
-        } else {
-        if (act) {
-          if (g == 0 && !reuse) fpart += PB::stage_cost(pc, par, sd_of(l, k), k, zs, zs + NX);
-          if (g == 0 && k == N - 1 && !reuse) fpart += PB::term_cost(pc, par, sd_of(l, N), xN);
+          if constexpr (!pb_symtab<PB>::value) {
 #pragma unroll
-          for (int c = 0; c < CPL; ++c) {
-            const int col = c0 + c;
-            if (col < NZ) l.grad[k * NZ + col] = is_free(pc, k, col) ? PB::cost_grad(pc, par, sd_of(l, k), k, col, zs) : 0.0;
-            if (col < NX && k == N - 1) l.grad[N * NZ + col] = PB::term_grad(pc, col, xN);
+            for (int c = 0; c < CPL; ++c)
+#pragma unroll
+              for (int r = 0; r < NZ; ++r) ch[r][c] = (c0 + c < NZ && r >= c0 + c) ? PB::cost_hess(pc, k, r, c0 + c) : 0.0;
           }
-        }
-#pragma unroll
-        for (int c = 0; c < CPL; ++c)
-#pragma unroll
-          for (int r = 0; r < NZ; ++r) ch[r][c] = (c0 + c < NZ && r >= c0 + c) ? PB::cost_hess(pc, k, r, c0 + c) : 0.0;
         }
       }
       DTICK(5)
@@ -3542,7 +3578,7 @@ __device__ __forceinline__ void ocp_solve_body(lds_double* lds_raw, const OcpCon
   for (it = 0;; ++it) {
     if constexpr (S::SYM) {
       if (pts_ok) {
-        OCP_FOR(e, N * NX) l.c[e] = l.ct[e];
+        if constexpr (!(OCP_SEAMS & 2)) OCP_FOR(e, N * NX) l.c[e] = l.ct[e];
         (void)S::eval_derivs_sym(lds_raw, wsb, true);
         fval = f_trial;
       } else fval = S::eval_derivs(lds_raw, wsb);
@@ -3574,7 +3610,9 @@ __device__ __forceinline__ void ocp_solve_body(lds_double* lds_raw, const OcpCon
     DTICK(14)
     OCP_TICK(PH_ERR)
     // ---- search direction with inertia correction (W&B Alg. IC) ----
+    DTICKR
     S::finish_rhs(l, mu);
+    DTICK(21)
     double delta = 0.0;
     bool first_try = true, solved = false;
     for (;;) {
@@ -3885,17 +3923,23 @@ __device__ __forceinline__ void ocp_solve_body(lds_double* lds_raw, const OcpCon
       }
       const int NV = N * NX;
       for (int base = 0; base < NV; base += OCP_TPB * U) {
-        double la[U], ln[U];
+        // (SYM policies: the accepted trial point's defects become the iterate's here - the derivative phase that follows takes
+        // them as given, `reuse`, and nothing reads l.c before it)
+        constexpr bool CT = S::SYM && (OCP_SEAMS & 2);
+        double la[U], ln[U], ctv[U];
         bool ok[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
           const int e0 = base + u * OCP_TPB + (int)threadIdx.x;
           ok[u] = e0 < NV;
           la[u] = l.lam[ok[u] ? e0 : 0]; ln[u] = l.lamn[ok[u] ? e0 : 0];
+          if constexpr (CT) ctv[u] = l.ct[ok[u] ? e0 : 0];
         }
 #pragma unroll
-        for (int u = 0; u < U; ++u)
+        for (int u = 0; u < U; ++u) {
           if (ok[u]) l.lam[base + u * OCP_TPB + (int)threadIdx.x] = la[u] + alpha * (ln[u] - la[u]);
+          if constexpr (CT) { if (ok[u]) l.c[base + u * OCP_TPB + (int)threadIdx.x] = ctv[u]; }
+        }
       }
     }
     if constexpr (NC > 0) {

@@ -19,6 +19,7 @@ it = int(nmpc._nlp_solution['iter_count'][0]) + 1
 print('derivative evaluations', it, [round(v / it) for v in out[:8]], '(0: stage points / their loads, 4: iterate + scalings, 5: cost terms)')
 print('riccati per call: backward loop, x0 part, forward sweep, recovery', [round(v / (it - 1)) for v in out[8:12]])
 print('errors: slot loops, reductions + scaling, tolerance test + barrier update', [round(v / it) for v in out[12:15]])
+print('right-hand side once mu is known (finish_rhs)', round(out[21] / (it - 1)))
 print('step: slot loop, reductions (+ barrier logs)', [round(v / (it - 1)) for v in out[15:17]])
 print('line search per iteration: form_trial, eval_values, acceptance tests', [round(v / (it - 1)) for v in out[17:20]])
 print('update', round(out[20] / (it - 1)))
