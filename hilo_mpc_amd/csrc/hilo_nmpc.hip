@@ -55,14 +55,47 @@ using namespace hilo;
   X(HILO_MODEL_ROBOT6, Robot6)           \
   X(HILO_MODEL_CSTR3, Cstr3)
 
-static int nmpc_model_dims(int id, int* nx, int* nu, int* np, size_t* lds, int N) {
+// developer switch, read at every launch like HILO_NMPC_TAYLOR: HILO_OCP_LAYOUT=runtime forces the instantiation with the run-time
+// LDS layout, so that the two can be compared in one process
+static bool nmpc_cap_layout(int N, int ncap) {
+  if (!OCP_LAYOUT_CAP || N > ncap) return false;
+  const char* e = getenv("HILO_OCP_LAYOUT");
+  return !(e && strcmp(e, "runtime") == 0);
+}
+
+// LDS bytes a launch of policy PB requests at horizon N (the choice of nmpc_launch_pb): what the size query below reports
+template <class PB>
+static size_t nmpc_track_lds(int N) {
+  using CAP = OcpCapLayout<PB>;
+  return nmpc_cap_layout(N, CAP::LAYOUT_N) ? CAP::cap_lds_bytes() : Ocp<PB>::lds_doubles(N) * sizeof(double);
+}
+
+// `taylor`: the footprint of the form with Taylor sweeps (sub-stepped integration, HILO_NMPC_TAYLOR) - its direction table is longer
+static int nmpc_model_dims(int id, int* nx, int* nu, int* np, size_t* lds, int N, bool taylor) {
   *lds = 0;
   switch (id) {
-#define X(ID, T) case ID: *nx = T::NX; *nu = T::NU; *np = T::NP; *lds = Ocp<NmpcTrack<T>>::lds_doubles(N) * sizeof(double); return HILO_OK;
+#define X(ID, T) case ID: *nx = T::NX; *nu = T::NU; *np = T::NP; \
+    *lds = taylor ? nmpc_track_lds<NmpcTrack<T, false, false>>(N) : nmpc_track_lds<NmpcTrack<T>>(N); return HILO_OK;
     HILO_NMPC_MODELS(X)
 #undef X
   }
   return fail(HILO_ENOTSUP, "model id %d has no NMPC instantiation in this build", id);
+}
+
+extern "C" int hilo_nmpc_layout_capacity(int model_id, int taylor, int* n_cap, long long* lds_cap, long long* lds_next) {
+  HILO_REQUIRE(n_cap && lds_cap && lds_next, "hilo_nmpc_layout_capacity: NULL argument");
+  switch (model_id) {
+#define X(ID, T) case ID: { \
+    using PS = NmpcTrack<T>; using PT = NmpcTrack<T, false, false>; \
+    const int n = taylor ? OcpCapLayout<PT>::LAYOUT_N : OcpCapLayout<PS>::LAYOUT_N; \
+    *n_cap = n; \
+    *lds_cap = (long long)((taylor ? Ocp<PT>::lds_doubles(n) : Ocp<PS>::lds_doubles(n)) * sizeof(double)); \
+    *lds_next = (long long)((taylor ? Ocp<PT>::lds_doubles(n + 1) : Ocp<PS>::lds_doubles(n + 1)) * sizeof(double)); \
+    return HILO_OK; }
+    HILO_NMPC_MODELS(X)
+#undef X
+  }
+  return fail(HILO_ENOTSUP, "model id %d has no NMPC instantiation in this build", model_id);
 }
 
 extern "C" void hilo_nmpc_destroy(hilo_nmpc* h) {
@@ -101,7 +134,7 @@ extern "C" int hilo_nmpc_create(const hilo_nmpc_desc* d, int device, hilo_nmpc**
     nx = d->user_nx; nu = d->user_nu; np = d->user_np;
     HILO_REQUIRE(nx >= 1 && nu >= 0 && np >= 0, "hilo_nmpc_create: bad user model dimensions");
   } else {
-    rc = nmpc_model_dims(d->model_id, &nx, &nu, &np, &lds, d->N);
+    rc = nmpc_model_dims(d->model_id, &nx, &nu, &np, &lds, d->N, d->n_sub > 1 || getenv("HILO_NMPC_TAYLOR") != nullptr);
     if (rc) return rc;
   }
   HILO_REQUIRE(nx <= OCP_MAXNX && nu <= OCP_MAXNU, "model too large for this build");
@@ -432,17 +465,33 @@ __global__ void nmpc_pack_par_kernel(int64_t batch, int np, int nu, const double
 }
 
 template <class PB>
-static int nmpc_launch_pb(hilo_nmpc* h, int64_t batch, const double* x0, const double* par, const double* v0, int64_t v0s,
-                          double* v_opt, double* f_opt, double* lam_g, double* u0, int32_t* status, int32_t* iters,
-                          double* kkt, hipStream_t s, int64_t par_stride, OcpExtra ex) {
-  if (h->lds_bytes > 64 * 1024)
+static int nmpc_launch_k(hilo_nmpc* h, size_t lds_bytes, int64_t batch, const double* x0, const double* par, const double* v0,
+                         int64_t v0s, double* v_opt, double* f_opt, double* lam_g, double* u0, int32_t* status, int32_t* iters,
+                         double* kkt, hipStream_t s, int64_t par_stride, OcpExtra ex) {
+  if (lds_bytes > 64 * 1024)
     HILO_HIP_CHECK(hipFuncSetAttribute((const void*)ocp_solve_kernel<PB, OCP_TPB>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)h->lds_bytes));
-  hipLaunchKernelGGL((ocp_solve_kernel<PB, OCP_TPB>), dim3((unsigned)batch), dim3(OCP_TPB), h->lds_bytes, s, h->dev, batch, x0, par,
+                                       (int)lds_bytes));
+  hipLaunchKernelGGL((ocp_solve_kernel<PB, OCP_TPB>), dim3((unsigned)batch), dim3(OCP_TPB), lds_bytes, s, h->dev, batch, x0, par,
                      par_stride, (const double*)nullptr, (int64_t)0, v0, v0s, 0, 0, v_opt, f_opt, lam_g, u0, 0,
                      status, iters, kkt, h->prof, (double*)nullptr, ex);
   HILO_HIP_CHECK(hipGetLastError());
   return HILO_OK;
+}
+
+template <class PB>
+static int nmpc_launch_pb(hilo_nmpc* h, int64_t batch, const double* x0, const double* par, const double* v0, int64_t v0s,
+                          double* v_opt, double* f_opt, double* lam_g, double* u0, int32_t* status, int32_t* iters,
+                          double* kkt, hipStream_t s, int64_t par_stride, OcpExtra ex) {
+  // Horizons up to the capacity horizon take the instantiation whose LDS layout is that of the capacity horizon, and request the
+  // capacity's footprint: more LDS than a short horizon needs, at no cost in residency - the kernel is pinned to one wave per SIMD
+  // (HILO_OCP_MINW = 1: four instances per CU), and the capacity is the largest horizon whose footprint stays within the 40 KB that
+  // let four instances share the 160 KB of a CU.  Longer horizons keep the run-time layout and their own footprint.
+  using CAP = OcpCapLayout<PB>;
+  if (nmpc_cap_layout(h->N, CAP::LAYOUT_N))
+    return nmpc_launch_k<CAP>(h, CAP::cap_lds_bytes(), batch, x0, par, v0, v0s, v_opt, f_opt, lam_g, u0, status, iters, kkt, s, par_stride,
+                              ex);
+  return nmpc_launch_k<PB>(h, Ocp<PB>::lds_doubles(h->N) * sizeof(double), batch, x0, par, v0, v0s, v_opt, f_opt, lam_g, u0, status, iters,
+                           kkt, s, par_stride, ex);
 }
 
 template <class M>

@@ -43,6 +43,12 @@ constexpr int OCP_MAXNC = 16;  // nonlinear inequality rows per stage (stage row
 #define HILO_OCP_SEAMS 3
 #endif
 constexpr int OCP_SEAMS = HILO_OCP_SEAMS;
+// build-out knob of the layout pass: -DHILO_OCP_LAYOUT_CAP=0 launches the precompiled tracking policies with the run-time LDS
+// layout only
+#ifndef HILO_OCP_LAYOUT_CAP
+#define HILO_OCP_LAYOUT_CAP 1
+#endif
+constexpr bool OCP_LAYOUT_CAP = HILO_OCP_LAYOUT_CAP != 0;
 constexpr int OCP_TPB = HILO_OCP_TPB;  // threads per instance (one or more waves)
 constexpr int OCP_NCOST = 2 * OCP_MAXNZ * OCP_MAXNZ + 4 * OCP_MAXNZ + 64;
 
@@ -298,6 +304,12 @@ template <class PB, class = void> struct pb_lam_fix { static constexpr bool valu
 template <class PB> struct pb_lam_fix<PB, void_tt<decltype(PB::LAM_FIX)>> { static constexpr bool value = PB::LAM_FIX; };
 template <class PB, class = void> struct pb_fused { static constexpr bool value = false; };
 template <class PB> struct pb_fused<PB, void_tt<decltype(PB::FUSED)>> { static constexpr bool value = PB::FUSED; };
+//   LAYOUT_N  > 0: the LDS layout is that of this horizon, whatever the horizon of the problem (<= LAYOUT_N) is: every array base
+//          is `base + constant` (no scalar register or arithmetic per base, accesses to different arrays pair into ds_read2 /
+//          ds_write2).  The run-time horizon still drives every loop and every index.  0: layout from the run-time horizon.
+//          Set by the wrapper OcpCapLayout below, never by a policy itself.
+template <class PB, class = void> struct pb_layout_n { static constexpr int value = 0; };
+template <class PB> struct pb_layout_n<PB, void_tt<decltype(PB::LAYOUT_N)>> { static constexpr int value = PB::LAYOUT_N; };
 
 // LDS / workspace footprint as plain functions of the dimensions (the host sizes run-time compiled problems with them)
 __host__ __device__ constexpr size_t ocp_iter_doubles(int NX, int NU, int NC, int N) {
@@ -412,6 +424,9 @@ struct Ocp {
   // gradient.  The matrices of the stages go to the workspace.  (Measured on C5: all eleven vectors in LDS cost a fourth resident
   // instance per CU and lost more than the shorter phases gained - 59.9 k against 67.5 k steps/s.)
   static constexpr int VEC_N = pb_vec_n<PB>::value;
+  // compile-time layout horizon (OcpCapLayout): LDS-resident iterates only, the workspace modes keep the run-time layout
+  static constexpr int LAYOUT_N = pb_layout_n<PB>::value;
+  static_assert(LAYOUT_N == 0 || !PB::BIG, "the capacity layout is for iterates in LDS");
   __host__ __device__ static constexpr size_t vec_doubles_level(int N, int level) {
     return (level >= 1 ? 7 * (size_t)(N + 1) * NZ : 0) + (level >= 2 ? 3 * (size_t)N * NX : 0) + (level >= 3 ? (size_t)(N + 1) * NZ : 0);
   }
@@ -470,9 +485,13 @@ struct Ocp {
   __device__ static int horizon_of(lds_double* base) {
     return reinterpret_cast<const __attribute__((address_space(3))) OcpConst*>(base)->N;
   }
-  __device__ static Lds carve(lds_double* base, double* ws) { return carve(base, ws, horizon_of(base)); }
-  __device__ static Lds carve(lds_double* base, double* ws, int N) {
+  __device__ static Lds carve(lds_double* base, double* ws) {
+    if constexpr (LAYOUT_N > 0) return carve(base, ws, LAYOUT_N);   // (no read of pc.N in front of the table)
+    else return carve(base, ws, horizon_of(base));
+  }
+  __device__ static Lds carve(lds_double* base, double* ws, int N_run) {
     Lds l;
+    const int N = LAYOUT_N > 0 ? LAYOUT_N : N_run;   // the horizon every array is SIZED for (indices stay those of the problem's)
     const size_t S = (size_t)(N + 1) * NZ;
     lds_double* q = base;
     auto take = [&](size_t n) { lds_double* r = q; q += n; return r; };
@@ -3483,6 +3502,21 @@ struct Ocp {
       if (e < SL) slot_store(e, in);
     }
   }
+};
+
+// The capacity layout of a policy whose iterate lives in LDS: the largest horizon whose footprint stays inside the 40 KB that let
+// four instances share a CU (VEC_BUDGET, the same figure the workspace modes size their LDS-resident vectors with) ...
+template <class PB> constexpr int ocp_layout_cap() {
+  int n = 0;
+  while (n < 512 && Ocp<PB>::lds_doubles(n + 1) * sizeof(double) <= Ocp<PB>::VEC_BUDGET) ++n;
+  return n;
+}
+// ... and the policy with that layout: the same problem, every array base a compile-time offset.  For horizons up to LAYOUT_N;
+// the launch requests OcpCapLayout<PB>::cap_lds_bytes() whatever the horizon is.
+template <class PB> struct OcpCapLayout : PB {
+  static_assert(!PB::BIG, "the capacity layout is for iterates in LDS");
+  static constexpr int LAYOUT_N = ocp_layout_cap<PB>();
+  static constexpr size_t cap_lds_bytes() { return Ocp<PB>::lds_doubles(LAYOUT_N) * sizeof(double); }
 };
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -538,6 +538,11 @@ int hilo_nmpc_solve_tv(hilo_nmpc* h, int64_t batch, const double* x0, const doub
    everything in front of the first iteration, finish = the write-back); enable != 0 starts collecting,
    cycles_host[10] (may be NULL) receives the last launch's counters */
 int hilo_nmpc_profile(hilo_nmpc* h, int enable, long long* cycles_host);
+/* the capacity horizon of a precompiled tracking model's LDS layout (taylor != 0: of its form with Taylor sweeps): the largest
+   horizon whose per-instance footprint stays within 40 KB - 64 B, so that four instances share a CU.  Horizons up to n_cap run
+   on a kernel whose array offsets are compile-time constants and request lds_cap bytes; lds_next: the footprint at n_cap + 1.
+   Needs no device. */
+int hilo_nmpc_layout_capacity(int model_id, int taylor, int* n_cap, long long* lds_cap, long long* lds_next);
 /* x+ = Phi(x, u, p) with the controller's own shooting map: closed-loop harness (control_loop.py:343-396) */
 int hilo_nmpc_plant_step(hilo_nmpc* h, int64_t batch, const double* x, const double* u, const double* p,
                          int64_t p_stride, double* x_next, void* stream);
