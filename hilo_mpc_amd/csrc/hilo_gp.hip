@@ -228,7 +228,7 @@ __global__ __launch_bounds__(FACT_TPB) void gp_factor_kernel(int n, double* __re
   // --- right-looking Cholesky ---------------------------------------------------------------
   for (int j = 0; j < n; ++j) {
     const double ajj = A[(int64_t)j * n + j];
-    if (t == 0 && !(ajj > 0.0)) bad = j + 1;
+    if (t == 0 && !(ajj > 0.0) && bad == 0) bad = j + 1;   // the FIRST bad pivot: everything after it is NaN
     const double d = sqrt(ajj);
     const double id = 1.0 / d;
     __syncthreads();
@@ -283,7 +283,7 @@ __global__ __launch_bounds__(FACT_TPB) void gp_factor_kernel(int n, double* __re
   (void)Linv;
 }
 
-// Blocked version of the above for training sets whose panel fits the LDS (n <= 512): right-looking Cholesky in 16-wide block
+// Blocked version of the above for training sets whose panel fits the LDS (n <= 560): right-looking Cholesky in 16-wide block
 // columns - diagonal block factored and inverted by one wave in LDS, panel L_ij = A_ij L_jj^-T by all threads into an LDS panel,
 // trailing update A_IK -= P_I P_K^T tile by tile on v_mfma_f64_16x16x4 (4 per 16 x 16 x 16 tile, the waves of the workgroup
 // share the tiles) - then alpha by blocked forward / backward substitution with the stored inverses of the diagonal blocks, and
