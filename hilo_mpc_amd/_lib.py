@@ -29,7 +29,7 @@ class KfDesc(C.Structure):
 
 
 class SimOpts(C.Structure):
-    """hilo_sim_opts: method 0 = the handle's own map, 1 = HILO_SIM_DOPRI5."""
+    """hilo_sim_opts: method 0 = the handle's own map, 1 = HILO_SIM_DOPRI5, 2 = HILO_SIM_BDF."""
     _fields_ = [('method', C.c_int32), ('max_steps', C.c_int32), ('rtol', C.c_double), ('atol', C.c_double), ('h0', C.c_double)]
 
 

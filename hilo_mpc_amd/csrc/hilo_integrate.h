@@ -163,6 +163,446 @@ HD int dopri5_interval(Dopri5Carry<M::NX>& c, double* x, const double* u, const 
   return c.status;
 }
 
+// ---- variable-order implicit integration ----------------------------------------------------------------------------------
+// `bdf_interval` is the variable-order (1..5) backward differentiation method of scipy's `BDF` (scipy/integrate/_ivp/bdf.py,
+// common.py::select_initial_step), restated statement by statement - the NDF constants, the table of backward differences D with
+// MAX_ORDER + 3 rows and its rescaling `change_D`, the simplified Newton iteration, the retry logic (a stale Jacobian is renewed
+// before the step is halved; I - c J is factorised again whenever c = h / alpha[order] changes), the error estimate, the count of
+// equal steps and the order selection - so that its step sequence can be compared with a solver everybody has.  What differs:
+//   Jacobian     exact, from M::ode on Dual numbers (the tests hand scipy the analytic one)
+//   linear algebra  LU with partial pivoting per lane; a vanishing or non-finite pivot and any non-finite Newton update count as
+//                a Newton failure (scipy warns and goes on with inf / nan); every acceptance is written as a comparison that a
+//                NaN fails
+//   change_D     U^T (R^T D) row by row instead of (R U)^T D: the same product, another order of the additions
+//   bounds       `max_steps` attempted steps per sampling instant; scipy has none
+// What is indexed by the order or by a pivot row - D, the Jacobian, its factors, the permutation - lives in a store of
+// `bdf_entries(NX)` doubles per instance that the caller provides: LDS on the device (entry e of lane l at [e * STRIDE + l]: one
+// double per lane at consecutive addresses, a wave's 64-bit accesses fall into distinct banks whatever row each lane asks for),
+// a plain array on the host.  Everything else is held in registers under compile-time indices.
+constexpr int SIM_BDF = 2;   // HILO_SIM_BDF
+constexpr int BDF_MAX_ORDER = 5, BDF_NEWTON_MAXITER = 4;
+constexpr double BDF_MIN_FACTOR = 0.2, BDF_MAX_FACTOR = 10.0;
+// Widest model the method is built for: (MAX_ORDER + 3) NX + 2 NX^2 + 2 NX doubles per lane in LDS, 64 lanes per workgroup - 104 KiB
+// of the 160 KiB of a compute unit at 8 states, 150 KiB at 10.  With the dense synthetic right-hand side of DOPRI5_MAX_NX: 8
+// states 425 registers and no scratch, 10 states all 512 and 132 bytes of scratch per lane.
+constexpr int BDF_MAX_NX = 8;
+constexpr int bdf_entries(int nx) { return (BDF_MAX_ORDER + 3) * nx + 2 * nx * nx + 2 * nx; }
+
+constexpr double BDF_KAPPA[6] = {0.0, -0.1850, -1.0 / 9, -0.0823, -0.0415, 0.0};
+constexpr double BDF_GAMMA[6] = {0.0, 1.0, 1.0 + 1.0 / 2, 1.0 + 1.0 / 2 + 1.0 / 3, 1.0 + 1.0 / 2 + 1.0 / 3 + 1.0 / 4,
+                                 1.0 + 1.0 / 2 + 1.0 / 3 + 1.0 / 4 + 1.0 / 5};
+// a table read under a run-time order: a sum of constants times 0 or 1 - exact, no table in memory and no branch (the chain of
+// conditionals was compiled into nested divergent regions whose else-copies tools/check_exec_prologue.py reports)
+#define HILO_BDF_PICK(k, EXPR)                                                                                                  \
+  ((double)((k) <= 0) * EXPR(0) + (double)((k) == 1) * EXPR(1) + (double)((k) == 2) * EXPR(2) + (double)((k) == 3) * EXPR(3) + \
+   (double)((k) == 4) * EXPR(4) + (double)((k) >= 5) * EXPR(5))
+#define HILO_BDF_GAMMA_(k) BDF_GAMMA[k]
+#define HILO_BDF_ALPHA_(k) ((1.0 - BDF_KAPPA[k]) * BDF_GAMMA[k])
+#define HILO_BDF_ERRC_(k) (BDF_KAPPA[k] * BDF_GAMMA[k] + 1.0 / ((k) + 1))
+HD double bdf_gamma(int k) { return HILO_BDF_PICK(k, HILO_BDF_GAMMA_); }
+HD double bdf_alpha(int k) { return HILO_BDF_PICK(k, HILO_BDF_ALPHA_); }
+HD double bdf_error_const(int k) { return HILO_BDF_PICK(k, HILO_BDF_ERRC_); }
+#undef HILO_BDF_PICK
+#undef HILO_BDF_GAMMA_
+#undef HILO_BDF_ALPHA_
+#undef HILO_BDF_ERRC_
+// compute_R(order, 1)[k][j] = prod_{m = 1..k} (m - 1 - j) / m: upper triangular, the same entries for every order
+constexpr double bdf_U(int k, int j) {
+  double r = 1.0;
+  for (int m = 1; m <= k; ++m) r *= (double)(m - 1 - j) / m;
+  return r;
+}
+
+// the store of one instance: MP = lds_double* (device) or double* (host)
+template <int NX, int STRIDE, class MP>
+struct BdfMem {
+  MP m;
+  static constexpr int O_J = (BDF_MAX_ORDER + 3) * NX, O_LU = O_J + NX * NX, O_W = O_LU + NX * NX, O_PIV = O_W + NX;
+  static_assert(O_PIV + NX == bdf_entries(NX), "bdf_entries and the layout of BdfMem disagree");
+  HD decltype(auto) D(int r, int i) const { return m[(r * NX + i) * STRIDE]; }          // D [MAX_ORDER + 3][NX]
+  HD decltype(auto) J(int i, int j) const { return m[(O_J + i * NX + j) * STRIDE]; }     // df/dx
+  HD decltype(auto) LU(int i, int j) const { return m[(O_LU + i * NX + j) * STRIDE]; }   // factors of I - c J, rows permuted
+  HD decltype(auto) W(int i) const { return m[(O_W + i) * STRIDE]; }                     // the right-hand side being permuted
+  HD decltype(auto) PIV(int i) const { return m[(O_PIV + i) * STRIDE]; }                 // row exchanged with row i
+};
+
+// what one instance carries from one step (and, inputs held, from one sampling instant) to the next, next to its store
+template <int NX>
+struct BdfCarry {
+  double t, t_bound;   // time since the start of the integration and its end (the roll-out's; with an input sequence the interval's)
+  double h;            // step size (scipy's h_abs)
+  int order, n_equal;
+  bool started;        // D, J and h belong to this integration
+  bool have_lu;        // the factors in the store belong to the current c (scipy's LU is not None)
+  int status, n_acc, n_rej, n_rhs, n_jac, n_lu;
+};
+
+template <int NX>
+HD void bdf_init(BdfCarry<NX>& c, double t_bound) {
+  c.t = 0.0;
+  c.t_bound = t_bound;
+  c.h = 0.0;
+  c.order = 1;
+  c.n_equal = 0;
+  c.started = c.have_lu = false;
+  c.status = SIM_OK;
+  c.n_acc = c.n_rej = c.n_rhs = c.n_jac = c.n_lu = 0;
+}
+// a new integration from the state handed to the next bdf_interval (the inputs jumped: the difference history is void); the
+// status and the counters go on
+template <int NX>
+HD void bdf_restart(BdfCarry<NX>& c, double t_bound) {
+  c.t = 0.0;
+  c.t_bound = t_bound;
+  c.started = c.have_lu = false;
+}
+
+// change_D: D[:order + 1] <- (R U)^T D[:order + 1] when the step size changes by `factor`
+template <int NX, class MEM>
+HD void bdf_change_D(const MEM& mem, int order, double factor) {
+  constexpr int N = BDF_MAX_ORDER + 1;
+#pragma unroll 1
+  for (int ix = 0; ix < NX; ++ix) {
+    double d[N], e[N];
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+      const double v = mem.D(i, ix);
+      d[i] = i <= order ? v : 0.0;
+    }
+    // e = R^T d with R = compute_R(order, factor), R[i][k] = prod_{m = 1..i} (m - 1 - factor k) / m: the leading block of the one
+    // for MAX_ORDER, its columns built as they are used (a 6 x 6 table kept over the loop costs 72 registers)
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+      double r = 1.0;
+      e[k] = d[0];
+#pragma unroll
+      for (int i = 1; i < N; ++i) {
+        r *= ((double)(i - 1) - factor * k) * (1.0 / i);
+        e[k] += r * d[i];
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+      double s = 0.0;
+#pragma unroll
+      for (int k = 0; k <= j; ++k) s += bdf_U(k, j) * e[k];
+      if (j <= order) mem.D(j, ix) = s;
+    }
+  }
+}
+
+// df/dx at x into the store, CH columns per evaluation of M::ode on Dual<CH>
+template <class M, class MEM>
+HD void bdf_jacobian(const MEM& mem, const double* x, const double* u, const double* p, double dt) {
+  constexpr int NX = M::NX, CH = NX < 4 ? NX : 4;
+#pragma unroll
+  for (int c0 = 0; c0 < NX; c0 += CH) {
+    Dual<CH> xd[NX], fd[NX];
+#pragma unroll
+    for (int i = 0; i < NX; ++i) {
+      xd[i] = Dual<CH>(x[i]);
+      if (i >= c0 && i < c0 + CH) xd[i].d[i - c0] = 1.0;
+    }
+    M::ode(xd, u, p, dt, fd);
+#pragma unroll
+    for (int i = 0; i < NX; ++i)
+#pragma unroll
+      for (int q = 0; q < CH; ++q)
+        if (c0 + q < NX) mem.J(i, c0 + q) = fd[i].d[q];
+  }
+}
+
+// factors of I - c J with partial pivoting, in place in the store; false for a vanishing or non-finite pivot.  The loops over rows
+// stay rolled: every operand is in the store under a run-time row anyway, and unrolled the compiler keeps the whole matrix in
+// registers across the elimination (at 8 states 80 registers more, at 10 the difference between none and 132 bytes of scratch).
+template <int NX, class MEM>
+HD bool bdf_factor(const MEM& mem, double c) {
+#pragma unroll 1
+  for (int i = 0; i < NX; ++i)
+    for (int j = 0; j < NX; ++j) mem.LU(i, j) = (i == j ? 1.0 : 0.0) - c * mem.J(i, j);
+#pragma unroll 1
+  for (int k = 0; k < NX; ++k) {
+    int piv = k;
+    double best = ::fabs(mem.LU(k, k));
+    for (int i = k + 1; i < NX; ++i) {
+      const double a = ::fabs(mem.LU(i, k));
+      if (a > best) { best = a; piv = i; }
+    }
+    if (!(best > 0.0 && best < INFINITY)) return false;
+    mem.PIV(k) = (double)piv;
+    if (piv != k)
+      for (int j = 0; j < NX; ++j) {
+        const double a = mem.LU(k, j), b = mem.LU(piv, j);
+        mem.LU(k, j) = b;
+        mem.LU(piv, j) = a;
+      }
+    const double inv = 1.0 / mem.LU(k, k);
+    for (int i = k + 1; i < NX; ++i) {
+      const double l = mem.LU(i, k) * inv;
+      mem.LU(i, k) = l;
+      for (int j = k + 1; j < NX; ++j) mem.LU(i, j) -= l * mem.LU(k, j);
+    }
+  }
+  return true;
+}
+
+// b <- (I - c J)^-1 b with the factors of bdf_factor
+template <int NX, class MEM>
+HD void bdf_solve(const MEM& mem, double* b) {
+#pragma unroll
+  for (int i = 0; i < NX; ++i) mem.W(i) = b[i];
+  for (int k = 0; k < NX; ++k) {
+    const int piv = (int)mem.PIV(k);
+    if (piv != k) {
+      const double a = mem.W(k), q = mem.W(piv);
+      mem.W(k) = q;
+      mem.W(piv) = a;
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < NX; ++i) b[i] = mem.W(i);
+#pragma unroll
+  for (int i = 1; i < NX; ++i)
+#pragma unroll
+    for (int j = 0; j < i; ++j) b[i] -= mem.LU(i, j) * b[j];
+#pragma unroll
+  for (int i = NX - 1; i >= 0; --i) {
+#pragma unroll
+    for (int j = i + 1; j < NX; ++j) b[i] -= mem.LU(i, j) * b[j];
+    b[i] /= mem.LU(i, i);
+  }
+}
+
+// Advances dx/dt = f(x, u, p) until the integration time reaches t_target (<= c.t_bound) and reads the state at t_target off the
+// interpolant of the difference table (scipy's BdfDenseOutput) into x.  A step may pass t_target - and later targets, which the
+// next calls then only interpolate; the end of the integration alone clips a step.  On the first call after bdf_init /
+// bdf_restart x is the initial state.  Returns c.status; on a failure x is left as it was (the caller discards it).  `max_steps`
+// bounds the attempted steps of this call, h0 > 0 is the first step.
+template <class M, class MEM>
+HD int bdf_interval(BdfCarry<M::NX>& c, const MEM& mem, double* x, const double* u, const double* p, double dt, double t_target,
+                    double rtol, double atol, double h0, int max_steps) {
+  constexpr int NX = M::NX;
+  constexpr double EPS = 2.220446049250313e-16;
+  if (c.status != SIM_OK) return c.status;
+  if (!c.started) {
+    double f0[NX];
+    M::ode(x, u, p, dt, f0);
+    ++c.n_rhs;
+    bdf_jacobian<M>(mem, x, u, p, dt);
+    ++c.n_jac;
+    if (h0 > 0.0) {
+      c.h = ::fmin(h0, c.t_bound);
+    } else {   // select_initial_step with order = 1
+      double scale[NX], x1[NX], f1[NX];
+#pragma unroll
+      for (int i = 0; i < NX; ++i) scale[i] = atol + ::fabs(x[i]) * rtol;
+      const double d0 = dopri5_rms<NX>(x, scale), d1 = dopri5_rms<NX>(f0, scale);
+      double hh = (d0 < 1e-5 || d1 < 1e-5) ? 1e-6 : 0.01 * d0 / d1;
+      hh = ::fmin(hh, c.t_bound);
+#pragma unroll
+      for (int i = 0; i < NX; ++i) x1[i] = x[i] + hh * f0[i];
+      M::ode(x1, u, p, dt, f1);
+      ++c.n_rhs;
+#pragma unroll
+      for (int i = 0; i < NX; ++i) f1[i] -= f0[i];
+      const double d2 = dopri5_rms<NX>(f1, scale) / hh;
+      const double h1 = (d1 <= 1e-15 && d2 <= 1e-15) ? ::fmax(1e-6, hh * 1e-3) : ::pow(0.01 / ::fmax(d1, d2), 0.5);
+      c.h = ::fmin(::fmin(100.0 * hh, h1), c.t_bound);
+      if (!(c.h > 0.0)) c.h = c.t_bound;   // a non-finite estimate: the Newton iteration below fails and finds the step (or gives up)
+    }
+    for (int r = 0; r < BDF_MAX_ORDER + 3; ++r)
+#pragma unroll
+      for (int i = 0; i < NX; ++i) mem.D(r, i) = r == 0 ? x[i] : (r == 1 ? f0[i] * c.h : 0.0);
+    c.t = 0.0;
+    c.order = 1;
+    c.n_equal = 0;
+    c.have_lu = false;
+    c.started = true;
+  }
+  const double newton_tol = ::fmax(10.0 * EPS / rtol, ::fmin(0.03, ::sqrt(rtol)));
+  int attempts = 0;
+  while (c.t < t_target) {   // one pass: scipy's _step_impl
+    const double min_step = 10.0 * (::nextafter(c.t, INFINITY) - c.t);
+    double h = c.h;
+    int order = c.order;
+    if (h < min_step) {
+      bdf_change_D<NX>(mem, order, min_step / h);
+      h = min_step;
+      c.n_equal = 0;
+    }
+    bool current_jac = false, accepted = false;
+    double t_new = c.t, safety = 0.0, error_norm = 0.0;
+    double scale[NX], d[NX];
+    while (!accepted) {
+      if (attempts >= max_steps) return c.status = SIM_MAX_STEPS;
+      if (!(h >= min_step)) return c.status = SIM_STEP_TOO_SMALL;
+      ++attempts;
+      t_new = c.t + h;
+      if (t_new > c.t_bound) {
+        t_new = c.t_bound;
+        bdf_change_D<NX>(mem, order, (t_new - c.t) / h);
+        c.n_equal = 0;
+        c.have_lu = false;
+      }
+      h = t_new - c.t;
+      double y_predict[NX], psi[NX], y[NX];
+#pragma unroll
+      for (int i = 0; i < NX; ++i) {
+        y_predict[i] = mem.D(0, i);
+        psi[i] = 0.0;
+      }
+      for (int j = 1; j <= order; ++j) {
+        const double g = bdf_gamma(j);
+#pragma unroll
+        for (int i = 0; i < NX; ++i) {
+          const double v = mem.D(j, i);
+          y_predict[i] += v;
+          psi[i] += v * g;
+        }
+      }
+      const double alpha = bdf_alpha(order);
+#pragma unroll
+      for (int i = 0; i < NX; ++i) {
+        scale[i] = atol + rtol * ::fabs(y_predict[i]);
+        psi[i] /= alpha;
+      }
+      const double cc = h / alpha;
+      bool converged = false;
+      int n_iter = 0;
+      while (!converged) {
+        if (!c.have_lu) {
+          c.have_lu = bdf_factor<NX>(mem, cc);
+          ++c.n_lu;
+        }
+        if (c.have_lu) {   // solve_bdf_system
+          double dy_norm_old = -1.0;   // (none yet)
+#pragma unroll
+          for (int i = 0; i < NX; ++i) {
+            d[i] = 0.0;
+            y[i] = y_predict[i];
+          }
+#pragma unroll 1
+          for (int k = 0; k < BDF_NEWTON_MAXITER; ++k) {
+            n_iter = k + 1;
+            double f[NX];
+            M::ode(y, u, p, dt, f);
+            ++c.n_rhs;
+            bool finite = true;
+#pragma unroll
+            for (int i = 0; i < NX; ++i) finite = finite && ::fabs(f[i]) < INFINITY;
+            if (!finite) break;
+#pragma unroll
+            for (int i = 0; i < NX; ++i) f[i] = cc * f[i] - psi[i] - d[i];
+            bdf_solve<NX>(mem, f);   // f: dy
+            const double dy_norm = dopri5_rms<NX>(f, scale);
+            if (!(dy_norm < INFINITY)) break;
+            const bool have_rate = dy_norm_old >= 0.0;
+            const double rate = dy_norm / dy_norm_old;
+            if (have_rate && !(rate < 1.0 && ::pow(rate, (double)(BDF_NEWTON_MAXITER - k)) / (1.0 - rate) * dy_norm <= newton_tol)) break;
+#pragma unroll
+            for (int i = 0; i < NX; ++i) {
+              y[i] += f[i];
+              d[i] += f[i];
+            }
+            if (dy_norm == 0.0 || (have_rate && rate / (1.0 - rate) * dy_norm < newton_tol)) {
+              converged = true;
+              break;
+            }
+            dy_norm_old = dy_norm;
+          }
+        }
+        if (!converged) {
+          if (current_jac) break;
+          bdf_jacobian<M>(mem, y_predict, u, p, dt);
+          ++c.n_jac;
+          c.have_lu = false;
+          current_jac = true;
+        }
+      }
+      if (!converged) {
+        h *= 0.5;
+        bdf_change_D<NX>(mem, order, 0.5);
+        c.n_equal = 0;
+        c.have_lu = false;
+        ++c.n_rej;
+        continue;
+      }
+      safety = 0.9 * (2 * BDF_NEWTON_MAXITER + 1) / (2 * BDF_NEWTON_MAXITER + n_iter);
+      const double ec = bdf_error_const(order);
+      double s = 0.0;
+#pragma unroll
+      for (int i = 0; i < NX; ++i) {
+        scale[i] = atol + rtol * ::fabs(y[i]);
+        const double q = ec * d[i] / scale[i];
+        s += q * q;
+      }
+      error_norm = ::sqrt(s / NX);
+      if (!(error_norm <= 1.0)) {   // (a non-finite estimate fails the comparison: a rejection)
+        const double factor = ::fmax(BDF_MIN_FACTOR, safety * ::pow(error_norm, -1.0 / (order + 1)));
+        h *= factor;
+        bdf_change_D<NX>(mem, order, factor);
+        c.n_equal = 0;   // the factors stay: the iteration had no trouble converging
+        ++c.n_rej;
+      } else {
+        accepted = true;
+      }
+    }
+    ++c.n_equal;
+    ++c.n_acc;
+    c.t = t_new;
+    c.h = h;
+    // D^{j+1} y_n = D^j y_n - D^j y_{n-1}, d = D^{order+1} y_n
+#pragma unroll
+    for (int i = 0; i < NX; ++i) {
+      mem.D(order + 2, i) = d[i] - mem.D(order + 1, i);
+      mem.D(order + 1, i) = d[i];
+    }
+    for (int j = order; j >= 0; --j)
+#pragma unroll
+      for (int i = 0; i < NX; ++i) mem.D(j, i) += mem.D(j + 1, i);
+    if (c.n_equal < order + 1) continue;
+    double sm = 0.0, sp = 0.0;
+    {
+      const double em = bdf_error_const(order - 1), ep = bdf_error_const(order + 1);
+#pragma unroll
+      for (int i = 0; i < NX; ++i) {
+        const double qm = em * mem.D(order, i) / scale[i], qp = ep * mem.D(order + 2, i) / scale[i];
+        sm += qm * qm;
+        sp += qp * qp;
+      }
+    }
+    const double error_m_norm = order > 1 ? ::sqrt(sm / NX) : INFINITY;
+    const double error_p_norm = order < BDF_MAX_ORDER ? ::sqrt(sp / NX) : INFINITY;
+    const double fm = ::pow(error_m_norm, -1.0 / order), f0 = ::pow(error_norm, -1.0 / (order + 1)),
+                 fp = ::pow(error_p_norm, -1.0 / (order + 2));
+    double fmax_ = fm;   // argmax: the first of equal ones
+    int delta = -1;
+    if (f0 > fmax_) { fmax_ = f0; delta = 0; }
+    if (fp > fmax_) { fmax_ = fp; delta = 1; }
+    if (order + delta < 1) delta = 0;   // (order 1: fm is 0 and can only win against two zeros)
+    order += delta;
+    c.order = order;
+    const double factor = ::fmin(BDF_MAX_FACTOR, safety * fmax_);
+    c.h *= factor;
+    bdf_change_D<NX>(mem, order, factor);
+    c.n_equal = 0;
+    c.have_lu = false;
+  }
+  // BdfDenseOutput at t_target
+  double acc[NX];
+#pragma unroll
+  for (int i = 0; i < NX; ++i) acc[i] = 0.0;
+  double prod = 1.0;
+  for (int j = 0; j < c.order; ++j) {
+    prod *= (t_target - (c.t - c.h * j)) / (c.h * (1 + j));
+#pragma unroll
+    for (int i = 0; i < NX; ++i) acc[i] += mem.D(j + 1, i) * prod;
+  }
+#pragma unroll
+  for (int i = 0; i < NX; ++i) x[i] = acc[i] + mem.D(0, i);
+  return c.status;
+}
+
 constexpr int ROLLOUT_TPB = 64;   // one wave per workgroup: a slow instance holds back 63 others, not 255
 
 // One instance per lane.  X [steps + 1][batch][NX] (row 0: x0), Y [steps][batch][NY] or null, stats [batch][4] (status, accepted,
@@ -174,12 +614,23 @@ constexpr int ROLLOUT_TPB = 64;   // one wave per workgroup: a slow instance hol
 // active); no value crosses lanes, so an instance's result does not depend on the instances it shares the wave with.  An
 // instance that fails (SIM_MAX_STEPS, SIM_STEP_TOO_SMALL) gets NaN for the sampling instant it did not reach and every later one.
 // METHOD: SIM_MAP / SIM_DOPRI5 builds that path alone (the library's kernels: each with the registers of its own path), -1 chooses
-// by sp.method at run time (the one kernel of a run-time compiled model).
+// by sp.method at run time between those two (the one kernel of a run-time compiled model that serves both).  SIM_BDF is a kernel
+// of its own in either case (rollout_bdf_body below): it needs `lds`, bdf_entries(NX) * ROLLOUT_TPB doubles of the workgroup.
+template <class M, class KP>
+__device__ __forceinline__ void rollout_bdf_body(const KP& kp, const SimParams& sp, int64_t batch, int steps,
+                                                 const double* __restrict__ x0, const double* __restrict__ up, int64_t up_stride,
+                                                 int64_t up_step, double* __restrict__ X, double* __restrict__ Y,
+                                                 int* __restrict__ stats, lds_double* lds);
+
 template <class M, int METHOD = -1, class KP>
 __device__ __forceinline__ void rollout_body(const KP& kp, const SimParams& sp, int64_t batch, int steps,
                                              const double* __restrict__ x0, const double* __restrict__ up, int64_t up_stride,
                                              int64_t up_step, double* __restrict__ X, double* __restrict__ Y,
-                                             int* __restrict__ stats) {
+                                             int* __restrict__ stats, lds_double* lds = nullptr) {
+  if constexpr (METHOD == SIM_BDF) {
+    rollout_bdf_body<M>(kp, sp, batch, steps, x0, up, up_stride, up_step, X, Y, stats, lds);
+    return;
+  }
   constexpr int NX = M::NX, NU = M::NU, NP = M::NP, NY = M::NY;
   const int64_t b = (int64_t)blockIdx.x * ROLLOUT_TPB + threadIdx.x;
   if (b >= batch) return;
@@ -212,6 +663,61 @@ __device__ __forceinline__ void rollout_body(const KP& kp, const SimParams& sp, 
 #pragma unroll
       for (int i = 0; i < NX; ++i) x[i] = xo[i];
     }
+    double* Xk = X + ((int64_t)(k + 1) * batch + b) * NX;
+#pragma unroll
+    for (int i = 0; i < NX; ++i) Xk[i] = ok ? x[i] : nan;
+    if constexpr (NY > 0) {
+      if (Y != nullptr) {
+        double yy[NY];
+        M::meas(x, u, p, kp.dt, yy);
+        double* Yk = Y + ((int64_t)k * batch + b) * NY;
+#pragma unroll
+        for (int i = 0; i < NY; ++i) Yk[i] = ok ? yy[i] : nan;
+      }
+    }
+  }
+  if (stats != nullptr) {
+    stats[b * 4 + 0] = c.status;
+    stats[b * 4 + 1] = c.n_acc;
+    stats[b * 4 + 2] = c.n_rej;
+    stats[b * 4 + 3] = c.n_rhs;
+  }
+}
+
+// The SIM_BDF path.  Inputs held over the roll-out (up_step == 0): ONE integration over [0, steps dt] whose state - difference
+// table, order, step size, Jacobian, factors - is carried across the sampling instants; a step may pass one or several of them and
+// their states are read off the interpolant (scipy's solve_ivp with t_eval, CVODES in normal mode).  An input sequence: the
+// right-hand side jumps at every instant, so each interval is an integration of its own from order 1 with a fresh first step.
+template <class M, class KP>
+__device__ __forceinline__ void rollout_bdf_body(const KP& kp, const SimParams& sp, int64_t batch, int steps,
+                                                 const double* __restrict__ x0, const double* __restrict__ up, int64_t up_stride,
+                                                 int64_t up_step, double* __restrict__ X, double* __restrict__ Y,
+                                                 int* __restrict__ stats, lds_double* lds) {
+  constexpr int NX = M::NX, NU = M::NU, NP = M::NP, NY = M::NY;
+  static_assert(!M::DISCRETE && NX <= BDF_MAX_NX, "SIM_BDF integrates a continuous model of at most BDF_MAX_NX states");
+  const int64_t b = (int64_t)blockIdx.x * ROLLOUT_TPB + threadIdx.x;
+  if (b >= batch) return;
+  double x[NX], upv[NU + NP > 0 ? NU + NP : 1];
+#pragma unroll
+  for (int i = 0; i < NX; ++i) {
+    x[i] = x0[b * NX + i];
+    X[b * NX + i] = x[i];
+  }
+  const BdfMem<NX, ROLLOUT_TPB, lds_double*> mem = {lds + threadIdx.x};
+  BdfCarry<NX> c;
+  const bool held = up_step == 0;
+  bdf_init(c, held ? steps * kp.dt : kp.dt);
+  const double nan = __builtin_nan("");
+  for (int k = 0; k < steps; ++k) {
+    if (k == 0 || !held) {
+      const double* src = up + (int64_t)k * up_step + b * up_stride;
+#pragma unroll
+      for (int i = 0; i < NU + NP; ++i) upv[i] = src[i];
+      if (k > 0) bdf_restart(c, kp.dt);
+    }
+    const double* u = upv;
+    const double* p = upv + NU;
+    const bool ok = bdf_interval<M>(c, mem, x, u, p, kp.dt, held ? (k + 1) * kp.dt : kp.dt, sp.rtol, sp.atol, sp.h0, sp.max_steps) == SIM_OK;
     double* Xk = X + ((int64_t)(k + 1) * batch + b) * NX;
 #pragma unroll
     for (int i = 0; i < NX; ++i) Xk[i] = ok ? x[i] : nan;

@@ -59,6 +59,8 @@ struct JitKfKernels {
   hipFunction_t team[2] = {nullptr, nullptr};    // the same on a team of lanes per instance (kf_team_body): small batches
   hipFunction_t rollout = nullptr;               // many sampling intervals per launch (hilo_integrate.h::rollout_body)
   int rollout_scratch = 0;                       // bytes of scratch per lane of that kernel (0: everything in registers)
+  hipFunction_t rollout_bdf = nullptr;           // the same with the implicit method (hilo_integrate.h::rollout_bdf_body, SIM_BDF)
+  int rollout_bdf_scratch = 0;                   // bytes of scratch per lane of that kernel
   hipFunction_t lqr_call = nullptr, lqr_linearize = nullptr;   // regulator gains and Jacobians of the model's map (hilo_lqr.h)
   int lqr_scratch = 0;                           // bytes of scratch per lane of the two (the larger)
   int lqr_ok = 0;                                // the two are built for this model (hilo_lqr.h::LqrModelOk)

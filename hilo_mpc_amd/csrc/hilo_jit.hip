@@ -424,6 +424,16 @@ extern "C" __global__ __launch_bounds__(ROLLOUT_TPB) void hilo_user_rollout(KfPa
                                                                             double* __restrict__ Y, int* __restrict__ stats) {
   rollout_body<UserModel>(kp, sp, batch, steps, x0, up, up_stride, up_step, X, Y, stats);
 }
+extern "C" __global__ __launch_bounds__(ROLLOUT_TPB) void hilo_user_rollout_bdf(KfParams kp, SimParams sp, int64_t batch, int steps,
+                                                                                const double* __restrict__ x0,
+                                                                                const double* __restrict__ up, int64_t up_stride,
+                                                                                int64_t up_step, double* __restrict__ X,
+                                                                                double* __restrict__ Y, int* __restrict__ stats) {
+  if constexpr (!UserModel::DISCRETE && UserModel::NX <= BDF_MAX_NX) {
+    __shared__ double bdf_lds[bdf_entries(UserModel::NX) * ROLLOUT_TPB];
+    rollout_body<UserModel, SIM_BDF>(kp, sp, batch, steps, x0, up, up_stride, up_step, X, Y, stats, (lds_double*)bdf_lds);
+  }
+}
 extern "C" __global__ __launch_bounds__(64) void hilo_user_lqr_call(KfParams kp, LqrParams o, int64_t batch, const double* __restrict__ x,
                                                                     const double* __restrict__ x_eq, const double* __restrict__ u_eq,
                                                                     const double* __restrict__ p, int64_t p_stride,
@@ -474,6 +484,8 @@ extern "C" __global__ void hilo_user_kf_info(int* o) {
   HILO_HIP_CHECK(hipModuleGetFunction(&k.team[1], mod, "hilo_user_kf_ut"));
   HILO_HIP_CHECK(hipModuleGetFunction(&k.rollout, mod, "hilo_user_rollout"));
   if (hipFuncGetAttribute(&k.rollout_scratch, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, k.rollout) != hipSuccess) k.rollout_scratch = 0;
+  HILO_HIP_CHECK(hipModuleGetFunction(&k.rollout_bdf, mod, "hilo_user_rollout_bdf"));
+  if (hipFuncGetAttribute(&k.rollout_bdf_scratch, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, k.rollout_bdf) != hipSuccess) k.rollout_bdf_scratch = 0;
   HILO_HIP_CHECK(hipModuleGetFunction(&k.lqr_call, mod, "hilo_user_lqr_call"));
   HILO_HIP_CHECK(hipModuleGetFunction(&k.lqr_linearize, mod, "hilo_user_lqr_linearize"));
   {

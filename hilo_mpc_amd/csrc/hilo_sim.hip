@@ -13,7 +13,12 @@ __global__ __launch_bounds__(ROLLOUT_TPB) void rollout_kernel(KfParams kp, SimPa
                                                               const double* __restrict__ x0, const double* __restrict__ up,
                                                               int64_t up_stride, int64_t up_step, double* __restrict__ X,
                                                               double* __restrict__ Y, int* __restrict__ stats) {
-  rollout_body<M, METHOD>(kp, sp, batch, steps, x0, up, up_stride, up_step, X, Y, stats);
+  if constexpr (METHOD == SIM_BDF) {
+    __shared__ double bdf_lds[bdf_entries(M::NX) * ROLLOUT_TPB];
+    rollout_body<M, SIM_BDF>(kp, sp, batch, steps, x0, up, up_stride, up_step, X, Y, stats, (lds_double*)bdf_lds);
+  } else {
+    rollout_body<M, METHOD>(kp, sp, batch, steps, x0, up, up_stride, up_step, X, Y, stats);
+  }
 }
 
 template <class M>
@@ -26,6 +31,12 @@ static int rollout_launch(const KfParams& kp, const SimParams& sp, int64_t batch
                          Y, stats);
     else
       return fail(HILO_ENOTSUP, "hilo_model_rollout: HILO_SIM_DOPRI5 on a discrete model");
+  } else if (sp.method == SIM_BDF) {
+    if constexpr (!M::DISCRETE && M::NX <= BDF_MAX_NX)
+      hipLaunchKernelGGL((rollout_kernel<M, SIM_BDF>), dim3(grid), dim3(ROLLOUT_TPB), 0, s, kp, sp, batch, steps, x0, up, us, ustep, X, Y,
+                         stats);
+    else
+      return fail(HILO_ENOTSUP, "hilo_model_rollout: HILO_SIM_BDF on a discrete model");
   } else {
     hipLaunchKernelGGL((rollout_kernel<M, SIM_MAP>), dim3(grid), dim3(ROLLOUT_TPB), 0, s, kp, sp, batch, steps, x0, up, us, ustep, X, Y,
                        stats);
@@ -39,7 +50,8 @@ static int rollout_launch(const KfParams& kp, const SimParams& sp, int64_t batch
 using namespace hilo;
 
 static_assert(HILO_SIM_DOPRI5_MAX_NX == DOPRI5_MAX_NX && HILO_SIM_DOPRI5 == SIM_DOPRI5 && HILO_SIM_STATUS_MAX_STEPS == SIM_MAX_STEPS &&
-              HILO_SIM_STATUS_STEP_TOO_SMALL == SIM_STEP_TOO_SMALL, "include/hilo_hip.h and csrc/hilo_integrate.h disagree");
+              HILO_SIM_STATUS_STEP_TOO_SMALL == SIM_STEP_TOO_SMALL && HILO_SIM_BDF == SIM_BDF && HILO_SIM_BDF_MAX_NX == BDF_MAX_NX,
+              "include/hilo_hip.h and csrc/hilo_integrate.h disagree");
 
 extern "C" int hilo_model_rollout(hilo_kf* kf, const hilo_sim_opts* opts, int64_t batch, int steps, const double* x0,
                                   const double* up, int64_t up_stride, int64_t up_step, double* X, double* Y, int32_t* stats,
@@ -48,7 +60,8 @@ extern "C" int hilo_model_rollout(hilo_kf* kf, const hilo_sim_opts* opts, int64_
   HILO_REQUIRE(batch >= 0 && steps >= 1, "hilo_model_rollout: need batch >= 0 and steps >= 1");
   SimParams sp = {SIM_MAP, 10000, 1e-6, 1e-8, 0.0};
   if (opts) {
-    HILO_REQUIRE(opts->method == HILO_SIM_MAP || opts->method == HILO_SIM_DOPRI5, "hilo_model_rollout: unknown method %d", opts->method);
+    HILO_REQUIRE(opts->method == HILO_SIM_MAP || opts->method == HILO_SIM_DOPRI5 || opts->method == HILO_SIM_BDF,
+                 "hilo_model_rollout: unknown method %d", opts->method);
     sp.method = opts->method;
     if (opts->max_steps > 0) sp.max_steps = opts->max_steps;
     if (opts->rtol > 0.0) sp.rtol = opts->rtol;
@@ -66,6 +79,17 @@ extern "C" int hilo_model_rollout(hilo_kf* kf, const hilo_sim_opts* opts, int64_
       return fail(HILO_ENOTSUP, "hilo_model_rollout: the compiled right-hand side of this model leaves HILO_SIM_DOPRI5 %d bytes of scratch "
                                 "memory per lane; the pair is built to keep its slopes in registers", kf->jit.rollout_scratch);
   }
+  if (sp.method == SIM_BDF) {
+    if (kf->discrete || !kf->kp.continuous)
+      return fail(HILO_ENOTSUP, "hilo_model_rollout: HILO_SIM_BDF integrates a continuous model; this handle holds a discrete "
+                                "(or discretised) one");
+    if (kf->nx > HILO_SIM_BDF_MAX_NX)
+      return fail(HILO_ENOTSUP, "hilo_model_rollout: HILO_SIM_BDF keeps its difference table, the Jacobian and its factors in the LDS of "
+                                "one workgroup and is built for up to %d states; the model has %d", HILO_SIM_BDF_MAX_NX, kf->nx);
+    if (kf->desc.model_id == 100 /* HILO_MODEL_USER */ && kf->jit.rollout_bdf_scratch > 0)
+      return fail(HILO_ENOTSUP, "hilo_model_rollout: the compiled right-hand side of this model leaves HILO_SIM_BDF %d bytes of scratch "
+                                "memory per lane; the method is built to keep its vectors in registers", kf->jit.rollout_bdf_scratch);
+  }
   if (batch == 0) return HILO_OK;
   HILO_REQUIRE(x0 && X, "hilo_model_rollout: NULL argument");
   HILO_REQUIRE(kf->nu + kf->np == 0 || up, "hilo_model_rollout: the model has %d inputs/parameters but `up` is NULL", kf->nu + kf->np);
@@ -79,11 +103,12 @@ extern "C" int hilo_model_rollout(hilo_kf* kf, const hilo_sim_opts* opts, int64_
   if (!up) up = &zero;   // never read (nu + np == 0); keeps the pointer arithmetic of the kernel defined
   int* st = (int*)stats;
   if (kf->desc.model_id == 100 /* HILO_MODEL_USER */) {
-    HILO_REQUIRE(kf->jit.rollout, "hilo_model_rollout: the run-time compiled roll-out kernel is not loaded");
+    hipFunction_t fn = sp.method == SIM_BDF ? kf->jit.rollout_bdf : kf->jit.rollout;
+    HILO_REQUIRE(fn, "hilo_model_rollout: the run-time compiled roll-out kernel is not loaded");
     KfParams kpv = kp;
     void* args[] = {&kpv, &sp, &batch, &steps, &x0, &up, &up_stride, &up_step, &X, &Y, &st};
     const unsigned grid = (unsigned)((batch + ROLLOUT_TPB - 1) / ROLLOUT_TPB);
-    HILO_HIP_CHECK(hipModuleLaunchKernel(kf->jit.rollout, grid, 1, 1, ROLLOUT_TPB, 1, 1, 0, s, args, nullptr));
+    HILO_HIP_CHECK(hipModuleLaunchKernel(fn, grid, 1, 1, ROLLOUT_TPB, 1, 1, 0, s, args, nullptr));
     return HILO_OK;
   }
   switch (kf->desc.model_id) {

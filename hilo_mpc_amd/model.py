@@ -37,7 +37,7 @@ ZOO_FUNCTOR = {'toy1d': 'Toy1D', 'bioreactor3': 'Bioreactor3', 'chemostat4': 'Ch
 MODEL_USER = 100    # HILO_MODEL_USER: the model is defined by expressions and compiled at setup (csrc/hilo_jit.hip)
 # `Model.setup(solver=...)`: integrators with error control and their options under CasADi's names (what the reference's
 # `solver_options` carries to `ca.integrator`), with CasADi's defaults for CVODES
-SOLVERS = {'dopri5': 1}            # name -> hilo_sim_opts.method (HILO_SIM_DOPRI5)
+SOLVERS = {'dopri5': 1, 'bdf': 2}  # name -> hilo_sim_opts.method (HILO_SIM_DOPRI5, HILO_SIM_BDF)
 SOLVER_OPTIONS = {'reltol': 1e-6, 'abstol': 1e-8, 'max_num_steps': 10000, 'first_step': 0.}
 SIM_STATUS = {0: 'ok', 1: 'max_num_steps reached', 2: 'step size too small'}     # HILO_SIM_STATUS_*
 
@@ -58,7 +58,7 @@ class Model:
     For `Model('lti', A=..., B=..., C=...)` the matrices define a discrete LTI system
     (`x+ = A x + B u`, `y = C x`, cf. tests/test_LMPC.py:8-19)."""
 
-    _solver = None              # `setup(solver=...)`: None = the fixed-step maps, 'dopri5' = integration with error control
+    _solver = None              # `setup(solver=...)`: None = the fixed-step maps, 'dopri5' / 'bdf' = integration with error control
     _solver_options = None
 
     def __init__(self, name=None, A=None, B=None, C=None, discrete=None, id=None, plot_backend=None, **kwargs):
@@ -529,7 +529,12 @@ class Model:
         solver: None keeps the fixed-step maps (a continuous model that was not discretised is simulated with eight classic
         Runge-Kutta steps per interval, no error control).  'dopri5' integrates a continuous model with the Dormand-Prince 5(4)
         pair under step-size control (csrc/hilo_integrate.h) wherever the model is simulated - `step`, `rollout`, `simulate`, the
-        plant of a `SimpleControlLoop` - where the reference integrates with CVODES.
+        plant of a `SimpleControlLoop` - where the reference integrates with CVODES.  'bdf' integrates it with variable-order
+        (1..5) backward differentiation formulas, a Newton iteration on the exact Jacobian and step size and order chosen per
+        instance (scipy's `BDF` restated on the device): the method for a stiff model, on which the explicit pair is bound by
+        stability and takes thousands of steps per interval or ends with 'max_num_steps reached'.  With inputs held over a
+        `rollout` the integrator's state is carried across the sampling instants (their states are interpolated, only the end
+        clips a step); with an input sequence every interval starts afresh.  Models of up to 8 states.
         solver_options, under CasADi's names (defaults: CasADi's for CVODES): reltol 1e-6, abstol 1e-8, max_num_steps 10000
         (attempted steps per sampling interval), first_step 0 (estimated)."""
         if self._symbolic and self._ode is None:
@@ -543,7 +548,7 @@ class Model:
             if self.discrete:
                 raise RuntimeError("Model is discrete. No solver is required.")
             if solver not in SOLVERS:
-                raise ValueError(f"Solver '{solver}' is not available on your system. Use {' or '.join(repr(q) for q in SOLVERS)} instead")
+                raise ValueError(f"Solver '{solver}' is not available on your system. Use 'dopri5' instead, or 'bdf' for a stiff model")
             if getattr(self, 'n_z', 0):
                 raise RuntimeError(f"Solver '{solver}' is not suitable for DAE systems. Use 'idas' or 'collocation' instead")
             opts = dict(SOLVER_OPTIONS)
@@ -805,7 +810,7 @@ class Model:
 
     def rollout(self, x0, u=None, p=None, steps=1, return_stats=False, device_index=None):
         """The many-interval sibling of `step`: `steps` sampling intervals for a batch of states in ONE launch
-        (`hilo_model_rollout`), with the model's own map or, after `setup(solver='dopri5')`, under error control.
+        (`hilo_model_rollout`), with the model's own map or, after `setup(solver='dopri5')` or `'bdf'`, under error control.
 
         x0 [B, n_x]; u [B, n_u] held over the roll-out or [steps, B, n_u] one row per sampling interval, p likewise; a batch axis
         of 1 is shared by the batch.  Returns x [steps + 1, B, n_x] (x[0] = x0) and y [steps, B, n_y] with y[k] = h(x[k + 1], u[k], p)

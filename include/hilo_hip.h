@@ -177,16 +177,24 @@ int hilo_kf_steps_split(hilo_kf* kf, int64_t batch, int steps, const double* xP,
    scipy's RK45), where the reference integrates with CVODES; inputs are held over a sampling interval, the step size is carried
    across sampling instants, and every sampling instant is hit exactly.  HILO_ENOTSUP for method 1 on a discrete handle, and for a
    model of more than HILO_SIM_DOPRI5_MAX_NX states or a run-time compiled one whose kernel needs scratch memory (the pair keeps its
-   slopes in registers).
+   slopes in registers).  method HILO_SIM_BDF: a continuous model integrated with variable-order (1..5) backward differentiation
+   formulas, step size and order chosen per instance (csrc/hilo_integrate.h: scipy's BDF statement by statement, the Jacobian
+   exact) - the method for a stiff model.  Inputs held over the roll-out (up_step 0): one integration whose state is carried across
+   the sampling instants, which are read off the interpolant, only the end of the roll-out clips a step; an input sequence: one
+   integration per sampling interval from order 1.  HILO_ENOTSUP for method 2 on a discrete handle, and for a model of more than
+   HILO_SIM_BDF_MAX_NX states or a run-time compiled one whose kernel needs scratch memory.
      x0 [B][nx];  up rows [u; p] like hilo_kf_steps: up_stride between instances (0: shared), up_step between sampling intervals
      (0: held over the roll-out, else [steps][B][nu+np]);  X [steps+1][B][nx] (row 0 is x0);  Y [steps][B][ny] = h(x_{k+1}, u_k, p)
      or NULL;  stats [B][4] int32 (status, accepted steps, rejected steps, right-hand-side evaluations) or NULL.
    An instance whose integration fails - more than max_steps attempted steps within ONE sampling interval
-   (HILO_SIM_STATUS_MAX_STEPS), or a step below 16 eps |t| (HILO_SIM_STATUS_STEP_TOO_SMALL) - ends with that status, and its rows
+   (HILO_SIM_STATUS_MAX_STEPS; HILO_SIM_BDF: between two consecutive sampling instants), or a step below 16 eps |t| (HILO_SIM_BDF: ten
+   spacings of t) (HILO_SIM_STATUS_STEP_TOO_SMALL) - ends with that status, and its rows
    from the sampling instant it did not reach onwards are NaN; the other instances are not affected and the call returns HILO_OK. */
 #define HILO_SIM_MAP 0
 #define HILO_SIM_DOPRI5 1
 #define HILO_SIM_DOPRI5_MAX_NX 12
+#define HILO_SIM_BDF 2
+#define HILO_SIM_BDF_MAX_NX 8
 #define HILO_SIM_STATUS_OK 0
 #define HILO_SIM_STATUS_MAX_STEPS 1
 #define HILO_SIM_STATUS_STEP_TOO_SMALL 2
