@@ -32,8 +32,9 @@ def _lit(v):
 class Emitter:
     """Collects statements for a set of expressions that share sub-expressions."""
 
-    def __init__(self, theta_index=None, x='x', u='u', p='p'):
+    def __init__(self, theta_index=None, x='x', u='u', p='p', time=None):
         self.theta_index, self.names = theta_index, {'x': x, 'u': u, 'p': p, 'z': 'z'}
+        self.time = time            # name of the time argument (a plain double) where the function being emitted has one
         self.lines, self.memo = [], {}
 
     def ref(self, e):
@@ -62,6 +63,11 @@ class Emitter:
             r = _lit(e.value)
         elif op in ('x', 'u', 'p', 'z'):
             r = f"{self.names[op]}[{int(e.value)}]"
+        elif op == 't':
+            if self.time is None:
+                raise NotImplementedError("the time t can only appear in the dynamical and measurement equations of a model that is "
+                                          "simulated (Model.step, rollout, simulate)")
+            r = self.time
         elif op == 'theta':
             if self.theta_index is None:
                 raise ValueError("a path variable can only appear where the path variable is defined (path references, costs)")
@@ -136,9 +142,13 @@ def model_source(n_x, n_u, n_p, ode, meas, discrete, helpers=(), symbolic=True, 
     """`struct UserModel` for the right-hand side `ode` (list of n_x expressions) and the measurement map `meas`; `helpers`:
     source of the functions the expressions call (learned terms with general kernels); symbolic=False leaves the symbolic
     derivative source out (a large network inside the model, Model.ANN_SYM_NODES: the engine keeps its Taylor sweeps); lqr_chunk: forward-mode
-    directions per pass of the linearisation kernels (csrc/hilo_lqr.h::LqrChunk; None = all of them up to six)."""
+    directions per pass of the linearisation kernels (csrc/hilo_lqr.h::LqrChunk; None = all of them up to six).
+    A model whose equations name the time t gets the time-aware functor (`time_variant_model_source`); every other model the source
+    it always got."""
     if len(ode) != n_x:
         raise ValueError(f"the model has {n_x} states but {len(ode)} dynamical equations")
+    if any(Expr.wrap(e).depends_on('t') for e in list(ode) + list(meas)):
+        return time_variant_model_source(n_x, n_u, n_p, ode, meas, discrete, helpers=helpers, lqr_chunk=lqr_chunk)
     em = Emitter()
     dx = [em.ref(e) for e in ode]
     body = em.lines + [f"    dx[{i}] = T({r});" for i, r in enumerate(dx)]
@@ -167,6 +177,39 @@ def model_source(n_x, n_u, n_p, ode, meas, discrete, helpers=(), symbolic=True, 
     return src
 
 
+def time_variant_model_source(n_x, n_u, n_p, ode, meas, discrete, helpers=(), lqr_chunk=None):
+    """`struct UserModel` of a model whose equations name the time: dx/dt = f(t, x, u, p) (or x+ = f(t, x, u, p)), y = h(t, x, u, p).
+    The functor declares TIME_VARIANT and carries `ode_t` / `meas_t` with the time - a plain double, a constant for every
+    derivative type - as their first argument (csrc/hilo_models.h::model_time_variant); the roll-out kernels hand it the time of
+    every evaluation (csrc/hilo_integrate.h).  The handle's other kernels - filters, particle function, linearisation - are compiled
+    against `ode` / `meas`, which evaluate at the FIXED time t = 0 so that they build; the library's entries that would launch them
+    refuse a time-variant model (HILO_ENOTSUP).  No symbolic derivative source: no consumer of it takes such a model."""
+    em = Emitter(time='t_abs')
+    dx = [em.ref(e) for e in ode]
+    body = em.lines + [f"    dx[{i}] = T({r});" for i, r in enumerate(dx)]
+    em2 = Emitter(time='t_abs')
+    yy = [em2.ref(e) for e in meas]
+    body2 = em2.lines + [f"    y[{i}] = T({r});" for i, r in enumerate(yy)]
+    return (''.join(helpers) +
+            f"struct UserModel {{\n"
+            f"  static constexpr int NX = {n_x}, NU = {n_u}, NP = {n_p}, NY = {len(meas)};\n"
+            f"  static constexpr bool DISCRETE = {'true' if discrete else 'false'};\n"
+            f"  static constexpr bool TIME_VARIANT = true;\n" +
+            (f"  static constexpr int LQR_CHUNK = {int(lqr_chunk)};\n" if lqr_chunk else "") +
+            f"  template <class T, class U, class P>\n"
+            f"  __device__ __forceinline__ static void ode_t(double t_abs, const T* x, const U* u, const P* p, double dt, T* dx) {{\n"
+            f"    (void)t_abs; (void)x; (void)u; (void)p; (void)dt;\n" + '\n'.join(body) + "\n  }\n"
+            f"  template <class T, class U, class P>\n"
+            f"  __device__ __forceinline__ static void meas_t(double t_abs, const T* x, const U* u, const P* p, double dt, T* y) {{\n"
+            f"    (void)t_abs; (void)x; (void)u; (void)p; (void)dt; (void)y;\n" + '\n'.join(body2) + "\n  }\n"
+            f"  template <class T, class U, class P>\n"
+            f"  __device__ __forceinline__ static void ode(const T* x, const U* u, const P* p, double dt, T* dx) {{\n"
+            f"    ode_t(0.0, x, u, p, dt, dx);\n  }}\n"
+            f"  template <class T, class U, class P>\n"
+            f"  __device__ __forceinline__ static void meas(const T* x, const U* u, const P* p, double dt, T* y) {{\n"
+            f"    meas_t(0.0, x, u, p, dt, y);\n  }}\n}};\n")
+
+
 def dae_model_source(n_x, n_u, n_p, n_z, ode, alg, meas, z_guess, alg_at_slope=False):
     """`struct UserModel` of a semi-explicit index-1 DAE  dx/dt = f(x, z, u, p),  0 = g(x, z, u, p).
     alg_at_slope: the reference's EXPLICIT Runge-Kutta transcription hands the algebraic equations the stage's SLOPE where the state
@@ -182,6 +225,9 @@ def dae_model_source(n_x, n_u, n_p, n_z, ode, alg, meas, z_guess, alg_at_slope=F
         raise ValueError("dimension mismatch between states and equations")
     if any(n.op in ('gp', 'gpk') for e in list(ode) + list(alg) for n in Expr.wrap(e).nodes().values()):
         raise NotImplementedError("a learned term inside a DAE model is not built")
+    if any(Expr.wrap(e).depends_on('t') for e in list(ode) + list(alg) + list(meas)):
+        raise NotImplementedError("explicit time dependence of a model with algebraic states is not built; time-variant models are "
+                                  "ordinary differential (or difference) equations")
     if alg_at_slope:
         odes = [Expr.wrap(e) for e in ode]
         alg = Expr.substitute([Expr.wrap(e) for e in alg], lambda n: odes[int(n.value)] if n.op == 'x' else None)

@@ -6,7 +6,9 @@ controller's model], cp=p)`, `plant.simulate(u=u, p=p)`, `observer.estimate()` -
 observer runs alongside.  Here the plant is advanced on the device: with the controller's shooting map when it is the
 controller's own model (`NMPC.plant_step`), with `Model.step` for a plant model of its own (a continuous plant is integrated with
 eight classic Runge-Kutta steps per interval, or - set up with `Model.setup(solver='dopri5')` - under error control like the
-reference's CVODES), or by a callable `(x, u, p) -> x+`.  A controller without `optimize` but with `call` (the LQR) is asked
+reference's CVODES), or by a callable `(x, u, p) -> x+`.  A time-variant plant (`Model.is_time_variant`) is advanced with
+`plant.simulate`, like the reference's, so that it keeps its clock: `run` starts it from x0 at the time of the plant's stored
+solution (`plant.set_initial_conditions(x0, t0=...)` beforehand chooses it; 0 otherwise).  A controller without `optimize` but with `call` (the LQR) is asked
 `u = controller.call(x=x, p=p)` (control_loop.py:377)."""
 import numpy as np
 import torch
@@ -31,7 +33,16 @@ class SimpleControlLoop:
                 if len(plant.input_names) != len(getattr(cm, 'input_names', plant.input_names)):
                     raise ValueError("plant and controller model have different numbers of inputs")
                 self._plant_fun, self._plant = (lambda x, u, p: plant.step(x, u, p)[0]), plant
+                if getattr(plant, 'is_time_variant', lambda: False)():
+                    self._plant_fun = self._simulate_plant
         self.solution = None
+
+    def _simulate_plant(self, x, u, p):
+        """One sampling interval of a time-variant plant through `simulate`, which holds the plant's time and advances it."""
+        plant = self._plant
+        plant.simulate(u=u, p=p, steps=1)
+        xn = plant._sim['x'][-1]
+        return torch.as_tensor(xn, device=x.device) if isinstance(x, torch.Tensor) else xn
 
     def _measure(self, x):
         obs = self._observer
@@ -49,6 +60,9 @@ class SimpleControlLoop:
         tensor = isinstance(x0, torch.Tensor)
         x = x0 if tensor else np.atleast_2d(np.asarray(x0, dtype=float))
         X, U, S, E = [x], [], [], []
+        if self._plant_fun == self._simulate_plant:        # the plant starts from x0 and goes on with its own clock
+            sim = getattr(self._plant, '_sim', None)
+            self._plant.set_initial_conditions(x, t0=sim['t'][-1] if sim else 0.)
         for _ in range(int(steps)):
             if hasattr(c, 'optimize'):
                 u = c.optimize(x, cp=p, **kwargs) if p is not None else c.optimize(x, **kwargs)   # control_loop.py:362

@@ -9,7 +9,22 @@
 //   controller   h <- h * clamp(0.9 err^(-1/5), 0.2, 10), at most 1 right after a rejection
 //   first step   Hairer, Norsett, Wanner I, II.4 (the estimate scipy uses)
 // The seventh slope of an accepted step is the first of the next (first same as last).  Inputs and parameters are held over a
-// sampling interval; the model functors are autonomous (their `ode` takes no time), t only enters the smallest admissible step.
+// sampling interval; time is not.
+//
+// Time.  A functor that declares TIME_VARIANT (hilo_models.h::model_time_variant) is handed the absolute time of every evaluation
+// through `ode_t` / `meas_t`; every other functor is autonomous, and for it the statements below are the ones they were before
+// time existed (the selection is `if constexpr` on the trait).  The carry structs hold the start time `t0` of what they integrate
+// next to their own clock `t`, which starts at 0: the absolute time is t0 + t (+ the position inside the interval).  The roll-out
+// forms the start of sampling interval k as t0 + k dt, never as a running sum.
+//   map          stage i of a sub-step of length h that starts at s is evaluated at s + c_i h (hilo_models.h::erk_c); a discrete
+//                model's map and measurement of interval k see t_k = t0 + k dt (the reference hands its discrete function ONE
+//                time per call, modules/base.py:1785-1795, :1882-1895)
+//   dopri5       stage times of scipy's RK45, C = (0, 1/5, 3/10, 4/5, 8/9, 1, 1); the first-step estimate evaluates f(t + h0, x + h0 f0);
+//                the slope kept from an accepted step was taken at the time and state the next step starts from
+//   bdf          fun(t_new, y) in the Newton iteration, f(t + h0, y1) in the first-step estimate, the Jacobian df/dx at the current
+//                (t, x) (no df/dt term, as in scipy)
+//   measurement  a continuous model's y[k] = h(t_k + dt, x_{k+1}, u_k, p) (modules/base.py:1729)
+// The smallest admissible step is measured against the absolute time in either method.
 //
 // Everything up to `rollout_body` is `HD` and templated on the functor like erk_step / rk4_classic, for doubles only: the same
 // statements compile for the host (tests/test_integrate_host.py builds a driver around this header and runs it on the CPU).
@@ -28,7 +43,7 @@ constexpr int SIM_OK = 0, SIM_MAX_STEPS = 1, SIM_STEP_TOO_SMALL = 2;   // HILO_S
 // either.  A wider model is refused by the host (HILO_ENOTSUP) instead of being left to spill.
 constexpr int DOPRI5_MAX_NX = 12;
 
-struct SimParams {   // mirrors hilo_sim_opts (include/hilo_hip.h)
+struct SimParams {   // mirrors hilo_sim_opts (include/hilo_hip.h) up to its start time, which is a kernel argument of its own
   int method, max_steps;
   double rtol, atol, h0;
 };
@@ -38,7 +53,8 @@ template <int NX>
 struct Dopri5Carry {
   double k1[NX];      // slope at the current state (valid when have_k1)
   double h;           // step-size proposal (0: not chosen yet)
-  double t;           // time since the start of the roll-out (only for the smallest admissible step)
+  double t;           // time since the start of the roll-out, at the start of the interval handed to dopri5_interval
+  double t0;          // absolute time of the start of the roll-out (a time-variant functor is evaluated at t0 + t + ...)
   int status, n_acc, n_rej, n_rhs;
   bool have_k1;
 };
@@ -46,7 +62,7 @@ struct Dopri5Carry {
 template <int NX>
 HD void dopri5_init(Dopri5Carry<NX>& c, double h0) {
   c.h = h0 > 0.0 ? h0 : 0.0;
-  c.t = 0.0;
+  c.t = c.t0 = 0.0;
   c.status = SIM_OK;
   c.n_acc = c.n_rej = c.n_rhs = 0;
   c.have_k1 = false;
@@ -63,7 +79,8 @@ HD double dopri5_rms(const double* v, const double* scale) {
   return ::sqrt(s / NX);
 }
 
-// Integrates dx/dt = f(x, u, p) over one sampling interval of length dt, in place.  Returns c.status; on a failure x holds the
+// Integrates dx/dt = f(x, u, p) - or f(c.t0 + c.t + tau, x, u, p), tau in [0, dt], for a time-variant functor - over one sampling
+// interval of length dt, in place.  Returns c.status; on a failure x holds the
 // state at the time the integration stopped (the caller discards it).  `max_steps` bounds the attempted steps of this call (the
 // meaning of CasADi's `max_num_steps`: per integrator call).
 template <class M>
@@ -79,13 +96,17 @@ HD int dopri5_interval(Dopri5Carry<M::NX>& c, double* x, const double* u, const 
   constexpr double A61 = 9017.0 / 3168, A62 = -355.0 / 33, A63 = 46732.0 / 5247, A64 = 49.0 / 176, A65 = -5103.0 / 18656;
   constexpr double B1 = 35.0 / 384, B3 = 500.0 / 1113, B4 = 125.0 / 192, B5 = -2187.0 / 6784, B6 = 11.0 / 84;
   constexpr double E1 = -71.0 / 57600, E3 = 71.0 / 16695, E4 = -71.0 / 1920, E5 = 17253.0 / 339200, E6 = -22.0 / 525, E7 = 1.0 / 40;
-  auto f = [&](const double* at, double* k) {
-    M::ode(at, u, p, dt, k);
+  constexpr bool TV = model_time_variant<M>::value;
+  constexpr double C2 = 1.0 / 5, C3 = 3.0 / 10, C4 = 4.0 / 5, C5 = 8.0 / 9;
+  double ts = 0.0;   // absolute time at the start of this interval (time-variant functors only)
+  if constexpr (TV) ts = c.t0 + c.t;
+  auto f = [&](double at_t, const double* at, double* k) {
+    model_ode_at<M>(at_t, at, u, p, dt, k);
     ++c.n_rhs;
   };
   if (c.status != SIM_OK) return c.status;
   if (!c.have_k1) {
-    f(x, c.k1);
+    f(ts, x, c.k1);
     c.have_k1 = true;
   }
   if (!(c.h > 0.0)) {   // the first step of the roll-out
@@ -97,7 +118,7 @@ HD int dopri5_interval(Dopri5Carry<M::NX>& c, double* x, const double* u, const 
     h0 = ::fmin(h0, dt);
 #pragma unroll
     for (int i = 0; i < NX; ++i) x1[i] = x[i] + h0 * c.k1[i];
-    f(x1, f1);
+    f(ts + h0, x1, f1);
 #pragma unroll
     for (int i = 0; i < NX; ++i) f1[i] -= c.k1[i];
     const double d2 = dopri5_rms<NX>(f1, scale) / h0;
@@ -110,31 +131,37 @@ HD int dopri5_interval(Dopri5Carry<M::NX>& c, double* x, const double* u, const 
   int attempts = 0;
   while (tl < dt) {
     if (attempts >= max_steps) return c.status = SIM_MAX_STEPS;
-    if (c.h < 16.0 * EPS * ::fabs(c.t + tl)) return c.status = SIM_STEP_TOO_SMALL;
+    if constexpr (TV) {
+      if (c.h < 16.0 * EPS * ::fabs(ts + tl)) return c.status = SIM_STEP_TOO_SMALL;
+    } else {
+      if (c.h < 16.0 * EPS * ::fabs(c.t + tl)) return c.status = SIM_STEP_TOO_SMALL;
+    }
     ++attempts;
     // clipped so that the sampling instant is hit exactly (a step that would leave a sliver of its own hundredth is stretched)
     const double rem = dt - tl;
     const bool last = 1.01 * c.h >= rem;
     const double h = last ? rem : c.h;
     double k2[NX], k3[NX], k4[NX], k5[NX], k6[NX], k7[NX], xi[NX], xn[NX];
+    double tn = 0.0;   // absolute time at the start of this step
+    if constexpr (TV) tn = ts + tl;
 #pragma unroll
     for (int i = 0; i < NX; ++i) xi[i] = x[i] + h * (A21 * c.k1[i]);
-    f(xi, k2);
+    f(tn + C2 * h, xi, k2);
 #pragma unroll
     for (int i = 0; i < NX; ++i) xi[i] = x[i] + h * (A31 * c.k1[i] + A32 * k2[i]);
-    f(xi, k3);
+    f(tn + C3 * h, xi, k3);
 #pragma unroll
     for (int i = 0; i < NX; ++i) xi[i] = x[i] + h * (A41 * c.k1[i] + A42 * k2[i] + A43 * k3[i]);
-    f(xi, k4);
+    f(tn + C4 * h, xi, k4);
 #pragma unroll
     for (int i = 0; i < NX; ++i) xi[i] = x[i] + h * (A51 * c.k1[i] + A52 * k2[i] + A53 * k3[i] + A54 * k4[i]);
-    f(xi, k5);
+    f(tn + C5 * h, xi, k5);
 #pragma unroll
     for (int i = 0; i < NX; ++i) xi[i] = x[i] + h * (A61 * c.k1[i] + A62 * k2[i] + A63 * k3[i] + A64 * k4[i] + A65 * k5[i]);
-    f(xi, k6);
+    f(tn + h, xi, k6);
 #pragma unroll
     for (int i = 0; i < NX; ++i) xn[i] = x[i] + h * (B1 * c.k1[i] + B3 * k3[i] + B4 * k4[i] + B5 * k5[i] + B6 * k6[i]);
-    f(xn, k7);
+    f(last ? ts + dt : tn + h, xn, k7);
     double s = 0.0;
 #pragma unroll
     for (int i = 0; i < NX; ++i) {
@@ -230,6 +257,7 @@ struct BdfMem {
 template <int NX>
 struct BdfCarry {
   double t, t_bound;   // time since the start of the integration and its end (the roll-out's; with an input sequence the interval's)
+  double t0;           // absolute time of the start of the integration (a time-variant functor is evaluated at t0 + t)
   double h;            // step size (scipy's h_abs)
   int order, n_equal;
   bool started;        // D, J and h belong to this integration
@@ -239,7 +267,7 @@ struct BdfCarry {
 
 template <int NX>
 HD void bdf_init(BdfCarry<NX>& c, double t_bound) {
-  c.t = 0.0;
+  c.t = c.t0 = 0.0;
   c.t_bound = t_bound;
   c.h = 0.0;
   c.order = 1;
@@ -249,7 +277,7 @@ HD void bdf_init(BdfCarry<NX>& c, double t_bound) {
   c.n_acc = c.n_rej = c.n_rhs = c.n_jac = c.n_lu = 0;
 }
 // a new integration from the state handed to the next bdf_interval (the inputs jumped: the difference history is void); the
-// status and the counters go on
+// status and the counters go on, and so does t0: the caller moves it to the new start
 template <int NX>
 HD void bdf_restart(BdfCarry<NX>& c, double t_bound) {
   c.t = 0.0;
@@ -291,9 +319,9 @@ HD void bdf_change_D(const MEM& mem, int order, double factor) {
   }
 }
 
-// df/dx at x into the store, CH columns per evaluation of M::ode on Dual<CH>
+// df/dx at (t, x) into the store, CH columns per evaluation of M::ode on Dual<CH> (t: read by a time-variant functor only)
 template <class M, class MEM>
-HD void bdf_jacobian(const MEM& mem, const double* x, const double* u, const double* p, double dt) {
+HD void bdf_jacobian(const MEM& mem, const double* x, const double* u, const double* p, double dt, double t = 0.0) {
   constexpr int NX = M::NX, CH = NX < 4 ? NX : 4;
 #pragma unroll
   for (int c0 = 0; c0 < NX; c0 += CH) {
@@ -303,7 +331,7 @@ HD void bdf_jacobian(const MEM& mem, const double* x, const double* u, const dou
       xd[i] = Dual<CH>(x[i]);
       if (i >= c0 && i < c0 + CH) xd[i].d[i - c0] = 1.0;
     }
-    M::ode(xd, u, p, dt, fd);
+    model_ode_at<M>(t, xd, u, p, dt, fd);
 #pragma unroll
     for (int i = 0; i < NX; ++i)
 #pragma unroll
@@ -373,7 +401,7 @@ HD void bdf_solve(const MEM& mem, double* b) {
   }
 }
 
-// Advances dx/dt = f(x, u, p) until the integration time reaches t_target (<= c.t_bound) and reads the state at t_target off the
+// Advances dx/dt = f(x, u, p) - or f(c.t0 + t, x, u, p) for a time-variant functor - until the integration time reaches t_target (<= c.t_bound) and reads the state at t_target off the
 // interpolant of the difference table (scipy's BdfDenseOutput) into x.  A step may pass t_target - and later targets, which the
 // next calls then only interpolate; the end of the integration alone clips a step.  On the first call after bdf_init /
 // bdf_restart x is the initial state.  Returns c.status; on a failure x is left as it was (the caller discards it).  `max_steps`
@@ -383,12 +411,13 @@ HD int bdf_interval(BdfCarry<M::NX>& c, const MEM& mem, double* x, const double*
                     double rtol, double atol, double h0, int max_steps) {
   constexpr int NX = M::NX;
   constexpr double EPS = 2.220446049250313e-16;
+  constexpr bool TV = model_time_variant<M>::value;
   if (c.status != SIM_OK) return c.status;
   if (!c.started) {
     double f0[NX];
-    M::ode(x, u, p, dt, f0);
+    model_ode_at<M>(c.t0, x, u, p, dt, f0);
     ++c.n_rhs;
-    bdf_jacobian<M>(mem, x, u, p, dt);
+    bdf_jacobian<M>(mem, x, u, p, dt, c.t0);
     ++c.n_jac;
     if (h0 > 0.0) {
       c.h = ::fmin(h0, c.t_bound);
@@ -401,7 +430,7 @@ HD int bdf_interval(BdfCarry<M::NX>& c, const MEM& mem, double* x, const double*
       hh = ::fmin(hh, c.t_bound);
 #pragma unroll
       for (int i = 0; i < NX; ++i) x1[i] = x[i] + hh * f0[i];
-      M::ode(x1, u, p, dt, f1);
+      model_ode_at<M>(c.t0 + hh, x1, u, p, dt, f1);
       ++c.n_rhs;
 #pragma unroll
       for (int i = 0; i < NX; ++i) f1[i] -= f0[i];
@@ -422,7 +451,13 @@ HD int bdf_interval(BdfCarry<M::NX>& c, const MEM& mem, double* x, const double*
   const double newton_tol = ::fmax(10.0 * EPS / rtol, ::fmin(0.03, ::sqrt(rtol)));
   int attempts = 0;
   while (c.t < t_target) {   // one pass: scipy's _step_impl
-    const double min_step = 10.0 * (::nextafter(c.t, INFINITY) - c.t);
+    double min_step;
+    if constexpr (TV) {
+      const double ta = c.t0 + c.t;
+      min_step = 10.0 * ::fabs(::nextafter(ta, INFINITY) - ta);
+    } else {
+      min_step = 10.0 * (::nextafter(c.t, INFINITY) - c.t);
+    }
     double h = c.h;
     int order = c.order;
     if (h < min_step) {
@@ -485,7 +520,7 @@ HD int bdf_interval(BdfCarry<M::NX>& c, const MEM& mem, double* x, const double*
           for (int k = 0; k < BDF_NEWTON_MAXITER; ++k) {
             n_iter = k + 1;
             double f[NX];
-            M::ode(y, u, p, dt, f);
+            model_ode_at<M>(c.t0 + t_new, y, u, p, dt, f);
             ++c.n_rhs;
             bool finite = true;
 #pragma unroll
@@ -513,7 +548,7 @@ HD int bdf_interval(BdfCarry<M::NX>& c, const MEM& mem, double* x, const double*
         }
         if (!converged) {
           if (current_jac) break;
-          bdf_jacobian<M>(mem, y_predict, u, p, dt);
+          bdf_jacobian<M>(mem, y_predict, u, p, dt, c.t0 + t_new);
           ++c.n_jac;
           c.have_lu = false;
           current_jac = true;
@@ -616,22 +651,28 @@ constexpr int ROLLOUT_TPB = 64;   // one wave per workgroup: a slow instance hol
 // METHOD: SIM_MAP / SIM_DOPRI5 builds that path alone (the library's kernels: each with the registers of its own path), -1 chooses
 // by sp.method at run time between those two (the one kernel of a run-time compiled model that serves both).  SIM_BDF is a kernel
 // of its own in either case (rollout_bdf_body below): it needs `lds`, bdf_entries(NX) * ROLLOUT_TPB doubles of the workgroup.
+// t0: the time of row 0 of X, one value for the batch; read for a time-variant functor only (the header's section on time).
+// hc [batch] or null (the host passes it with SIM_DOPRI5 only): the step-size proposal of each instance, taken over where positive
+// and written back at the end.  With the slope at the start recomputed at the same time and state it is all the pair carries across
+// a sampling instant, so a roll-out continued in a second launch takes the steps that one launch would have taken.
 template <class M, class KP>
 __device__ __forceinline__ void rollout_bdf_body(const KP& kp, const SimParams& sp, int64_t batch, int steps,
                                                  const double* __restrict__ x0, const double* __restrict__ up, int64_t up_stride,
                                                  int64_t up_step, double* __restrict__ X, double* __restrict__ Y,
-                                                 int* __restrict__ stats, lds_double* lds);
+                                                 int* __restrict__ stats, lds_double* lds, double t0 = 0.0);
 
 template <class M, int METHOD = -1, class KP>
 __device__ __forceinline__ void rollout_body(const KP& kp, const SimParams& sp, int64_t batch, int steps,
                                              const double* __restrict__ x0, const double* __restrict__ up, int64_t up_stride,
                                              int64_t up_step, double* __restrict__ X, double* __restrict__ Y,
-                                             int* __restrict__ stats, lds_double* lds = nullptr) {
+                                             int* __restrict__ stats, lds_double* lds = nullptr, double t0 = 0.0,
+                                             double* __restrict__ hc = nullptr) {
   if constexpr (METHOD == SIM_BDF) {
-    rollout_bdf_body<M>(kp, sp, batch, steps, x0, up, up_stride, up_step, X, Y, stats, lds);
+    rollout_bdf_body<M>(kp, sp, batch, steps, x0, up, up_stride, up_step, X, Y, stats, lds, t0);
     return;
   }
   constexpr int NX = M::NX, NU = M::NU, NP = M::NP, NY = M::NY;
+  constexpr bool TV = model_time_variant<M>::value;
   const int64_t b = (int64_t)blockIdx.x * ROLLOUT_TPB + threadIdx.x;
   if (b >= batch) return;
   double x[NX], upv[NU + NP > 0 ? NU + NP : 1];
@@ -643,8 +684,17 @@ __device__ __forceinline__ void rollout_body(const KP& kp, const SimParams& sp, 
   constexpr bool ADAPTIVE = !M::DISCRETE && NX <= DOPRI5_MAX_NX;
   Dopri5Carry<ADAPTIVE ? NX : 1> c;
   dopri5_init(c, sp.h0);
+  if constexpr (TV) c.t0 = t0;
+  if constexpr (ADAPTIVE && METHOD != SIM_MAP) {
+    if (hc != nullptr && hc[b] > 0.0) c.h = hc[b];   // a roll-out that goes on where another ended, with the step it would have tried
+  }
   const double nan = __builtin_nan("");
   for (int k = 0; k < steps; ++k) {
+    double tk = 0.0;   // the start of this sampling interval
+    if constexpr (TV) {
+      c.t = k * kp.dt;
+      tk = t0 + c.t;
+    }
     if (k == 0 || up_step != 0) {
       const double* src = up + (int64_t)k * up_step + b * up_stride;
 #pragma unroll
@@ -658,8 +708,8 @@ __device__ __forceinline__ void rollout_body(const KP& kp, const SimParams& sp, 
       if constexpr (ADAPTIVE && METHOD != SIM_MAP) ok = dopri5_interval<M>(c, x, u, p, kp.dt, sp.rtol, sp.atol, sp.max_steps) == SIM_OK;
     } else if constexpr (METHOD != SIM_DOPRI5) {
       double xo[NX];
-      if (kp.continuous && !M::DISCRETE) model_step<M>(4, kp.n_sub, x, u, p, kp.dt, xo);
-      else model_step<M>(kp.erk_order, kp.n_sub, x, u, p, kp.dt, xo);
+      if (kp.continuous && !M::DISCRETE) model_step<M>(4, kp.n_sub, x, u, p, kp.dt, xo, NoExt(), tk);
+      else model_step<M>(kp.erk_order, kp.n_sub, x, u, p, kp.dt, xo, NoExt(), tk);
 #pragma unroll
       for (int i = 0; i < NX; ++i) x[i] = xo[i];
     }
@@ -669,7 +719,8 @@ __device__ __forceinline__ void rollout_body(const KP& kp, const SimParams& sp, 
     if constexpr (NY > 0) {
       if (Y != nullptr) {
         double yy[NY];
-        M::meas(x, u, p, kp.dt, yy);
+        // a continuous model is measured at the end of the interval, a discrete one at the time its map was handed
+        model_meas_at<M>(M::DISCRETE ? tk : tk + kp.dt, x, u, p, kp.dt, yy);
         double* Yk = Y + ((int64_t)k * batch + b) * NY;
 #pragma unroll
         for (int i = 0; i < NY; ++i) Yk[i] = ok ? yy[i] : nan;
@@ -682,18 +733,23 @@ __device__ __forceinline__ void rollout_body(const KP& kp, const SimParams& sp, 
     stats[b * 4 + 2] = c.n_rej;
     stats[b * 4 + 3] = c.n_rhs;
   }
+  if constexpr (ADAPTIVE && METHOD != SIM_MAP) {
+    if (hc != nullptr) hc[b] = c.h;
+  }
 }
 
 // The SIM_BDF path.  Inputs held over the roll-out (up_step == 0): ONE integration over [0, steps dt] whose state - difference
 // table, order, step size, Jacobian, factors - is carried across the sampling instants; a step may pass one or several of them and
 // their states are read off the interpolant (scipy's solve_ivp with t_eval, CVODES in normal mode).  An input sequence: the
 // right-hand side jumps at every instant, so each interval is an integration of its own from order 1 with a fresh first step.
+// A time-variant functor sees the integration's own clock plus its start: t0 with the inputs held, t0 + k dt at a restart.
 template <class M, class KP>
 __device__ __forceinline__ void rollout_bdf_body(const KP& kp, const SimParams& sp, int64_t batch, int steps,
                                                  const double* __restrict__ x0, const double* __restrict__ up, int64_t up_stride,
                                                  int64_t up_step, double* __restrict__ X, double* __restrict__ Y,
-                                                 int* __restrict__ stats, lds_double* lds) {
+                                                 int* __restrict__ stats, lds_double* lds, double t0) {
   constexpr int NX = M::NX, NU = M::NU, NP = M::NP, NY = M::NY;
+  constexpr bool TV = model_time_variant<M>::value;
   static_assert(!M::DISCRETE && NX <= BDF_MAX_NX, "SIM_BDF integrates a continuous model of at most BDF_MAX_NX states");
   const int64_t b = (int64_t)blockIdx.x * ROLLOUT_TPB + threadIdx.x;
   if (b >= batch) return;
@@ -707,13 +763,17 @@ __device__ __forceinline__ void rollout_bdf_body(const KP& kp, const SimParams& 
   BdfCarry<NX> c;
   const bool held = up_step == 0;
   bdf_init(c, held ? steps * kp.dt : kp.dt);
+  if constexpr (TV) c.t0 = t0;
   const double nan = __builtin_nan("");
   for (int k = 0; k < steps; ++k) {
     if (k == 0 || !held) {
       const double* src = up + (int64_t)k * up_step + b * up_stride;
 #pragma unroll
       for (int i = 0; i < NU + NP; ++i) upv[i] = src[i];
-      if (k > 0) bdf_restart(c, kp.dt);
+      if (k > 0) {
+        bdf_restart(c, kp.dt);
+        if constexpr (TV) c.t0 = t0 + k * kp.dt;
+      }
     }
     const double* u = upv;
     const double* p = upv + NU;
@@ -724,7 +784,7 @@ __device__ __forceinline__ void rollout_bdf_body(const KP& kp, const SimParams& 
     if constexpr (NY > 0) {
       if (Y != nullptr) {
         double yy[NY];
-        M::meas(x, u, p, kp.dt, yy);
+        model_meas_at<M>(t0 + (k + 1) * kp.dt, x, u, p, kp.dt, yy);
         double* Yk = Y + ((int64_t)k * batch + b) * NY;
 #pragma unroll
         for (int i = 0; i < NY; ++i) Yk[i] = ok ? yy[i] : nan;

@@ -64,6 +64,7 @@ struct JitKfKernels {
   hipFunction_t lqr_call = nullptr, lqr_linearize = nullptr;   // regulator gains and Jacobians of the model's map (hilo_lqr.h)
   int lqr_scratch = 0;                           // bytes of scratch per lane of the two (the larger)
   int lqr_ok = 0;                                // the two are built for this model (hilo_lqr.h::LqrModelOk)
+  int time_variant = 0;                          // the functor declares TIME_VARIANT: only the two roll-out kernels hand it the time
   int dims[5] = {0, 0, 0, 0, 0};
   const double** gp_table = nullptr;   // device address of the module's hilo_user_gp[4] (learned terms of the user model)
   hipModule_t owned = nullptr;         // a module instance of the filter's own (private_module): unloaded with the handle

@@ -421,17 +421,19 @@ extern "C" __global__ __launch_bounds__(ROLLOUT_TPB) void hilo_user_rollout(KfPa
                                                                             const double* __restrict__ x0,
                                                                             const double* __restrict__ up, int64_t up_stride,
                                                                             int64_t up_step, double* __restrict__ X,
-                                                                            double* __restrict__ Y, int* __restrict__ stats) {
-  rollout_body<UserModel>(kp, sp, batch, steps, x0, up, up_stride, up_step, X, Y, stats);
+                                                                            double* __restrict__ Y, int* __restrict__ stats,
+                                                                            double t0, double* __restrict__ hc) {
+  rollout_body<UserModel>(kp, sp, batch, steps, x0, up, up_stride, up_step, X, Y, stats, nullptr, t0, hc);
 }
 extern "C" __global__ __launch_bounds__(ROLLOUT_TPB) void hilo_user_rollout_bdf(KfParams kp, SimParams sp, int64_t batch, int steps,
                                                                                 const double* __restrict__ x0,
                                                                                 const double* __restrict__ up, int64_t up_stride,
                                                                                 int64_t up_step, double* __restrict__ X,
-                                                                                double* __restrict__ Y, int* __restrict__ stats) {
+                                                                                double* __restrict__ Y, int* __restrict__ stats,
+                                                                                double t0) {
   if constexpr (!UserModel::DISCRETE && UserModel::NX <= BDF_MAX_NX) {
     __shared__ double bdf_lds[bdf_entries(UserModel::NX) * ROLLOUT_TPB];
-    rollout_body<UserModel, SIM_BDF>(kp, sp, batch, steps, x0, up, up_stride, up_step, X, Y, stats, (lds_double*)bdf_lds);
+    rollout_body<UserModel, SIM_BDF>(kp, sp, batch, steps, x0, up, up_stride, up_step, X, Y, stats, (lds_double*)bdf_lds, t0);
   }
 }
 extern "C" __global__ __launch_bounds__(64) void hilo_user_lqr_call(KfParams kp, LqrParams o, int64_t batch, const double* __restrict__ x,
@@ -452,6 +454,7 @@ extern "C" __global__ __launch_bounds__(64) void hilo_user_lqr_linearize(KfParam
 extern "C" __global__ void hilo_user_kf_info(int* o) {
   o[0] = UserModel::NX; o[1] = UserModel::NU; o[2] = UserModel::NP; o[3] = UserModel::NY; o[4] = UserModel::DISCRETE ? 1 : 0;
   o[5] = LqrModelOk<UserModel>::value ? 1 : 0;
+  o[6] = model_time_variant<UserModel>::value ? 1 : 0;
 }
 )";
   std::vector<std::string> opts;
@@ -500,10 +503,11 @@ extern "C" __global__ void hilo_user_kf_info(int* o) {
   HILO_HIP_CHECK(hipMalloc((void**)&dinfo, sizeof(int) * 8));
   void* args[] = {&dinfo};
   HILO_HIP_CHECK(hipModuleLaunchKernel(info, 1, 1, 1, 1, 1, 1, 0, nullptr, args, nullptr));
-  int hinfo[6];
-  HILO_HIP_CHECK(hipMemcpy(hinfo, dinfo, sizeof(int) * 6, hipMemcpyDeviceToHost));
+  int hinfo[7];
+  HILO_HIP_CHECK(hipMemcpy(hinfo, dinfo, sizeof(int) * 7, hipMemcpyDeviceToHost));
   for (int i = 0; i < 5; ++i) k.dims[i] = hinfo[i];
   k.lqr_ok = hinfo[5];
+  k.time_variant = hinfo[6];
   HILO_HIP_CHECK(hipFree(dinfo));
   {
     hipDeviceptr_t gptr = nullptr;

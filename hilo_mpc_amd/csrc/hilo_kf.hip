@@ -259,6 +259,7 @@ static int kf_run(hilo_kf* kf, int mode, int64_t batch, const double* in, const 
                   int64_t us, const double* Q, int64_t qs, const double* R, int64_t rs, double* out, double* yp,
                   void* stream) {
   HILO_REQUIRE(kf, "hilo_kf: NULL handle");
+  HILO_REFUSE_TIME_VARIANT(kf, "hilo_kf");
   HILO_REQUIRE(batch >= 0, "hilo_kf: negative batch");
   if (batch == 0) return HILO_OK;
   HILO_REQUIRE(in && out, "hilo_kf: NULL tile pointer");
@@ -350,6 +351,7 @@ static int kf_steps_impl(hilo_kf* kf, int64_t batch, int steps, const double* xP
                          int64_t q_stride, const double* R, int64_t r_stride, double* xP_out, int keep_all, double* y_pred,
                          void* stream) {
   HILO_REQUIRE(kf, "hilo_kf_steps: NULL handle");
+  HILO_REFUSE_TIME_VARIANT(kf, "hilo_kf_steps");
   HILO_REQUIRE(batch >= 0 && steps >= 1, "hilo_kf_steps: need batch >= 0 and steps >= 1");
   if (batch == 0) return HILO_OK;
   HILO_REQUIRE(xP && xP_out && y && y_pred && Q && R, "hilo_kf_steps: NULL argument");
@@ -417,6 +419,7 @@ extern "C" int hilo_pf_function(hilo_kf* kf, int64_t batch, int n_samples, const
                                 int64_t up_stride, const double* w, const double* v, const double* R, int64_t r_stride,
                                 double* X_prop, double* Y, double* q, void* stream) {
   HILO_REQUIRE(kf, "hilo_pf_function: NULL handle");
+  HILO_REFUSE_TIME_VARIANT(kf, "hilo_pf_function");
   HILO_REQUIRE(batch >= 0 && n_samples >= 1, "hilo_pf_function: need batch >= 0 and n_samples >= 1");
   if (batch == 0) return HILO_OK;
   HILO_REQUIRE(X && y && w && v && R && X_prop && Y && q, "hilo_pf_function: NULL argument");

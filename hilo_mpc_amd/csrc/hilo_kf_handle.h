@@ -14,6 +14,15 @@ struct hilo_kf {
   double* user_gp_pack[4] = {nullptr, nullptr, nullptr, nullptr};   // packed learned terms of that model (gp_pack_se)
 };
 
+// A time-variant model (hilo_models.h::model_time_variant) is handed the time by hilo_model_rollout alone.  Its other kernels are
+// compiled against the functor's autonomous `ode` / `meas`, which evaluate at t = 0, and the entries that would launch them refuse.
+#define HILO_REFUSE_TIME_VARIANT(kf, who)                                                                                        \
+  do {                                                                                                                          \
+    if ((kf)->jit.time_variant)                                                                                                 \
+      return hilo::fail(HILO_ENOTSUP, "%s: the model depends on time explicitly; only hilo_model_rollout hands a model the time "  \
+                                      "(Model.step, rollout, simulate)", who);                                                  \
+  } while (0)
+
 #define HILO_KF_MODELS(X)                 \
   X(HILO_MODEL_TOY1D, Toy1D)              \
   X(HILO_MODEL_BIOREACTOR3, Bioreactor3)  \

@@ -71,6 +71,7 @@ static int lqr_linearize_launch(const KfParams& kp, int64_t batch, const double*
 // what both handle-based entries check: a discrete-time map of an admitted size, and a loaded kernel without scratch memory
 static int lqr_check_handle(const hilo_kf* kf, const char* who) {
   HILO_REQUIRE(kf, "%s: NULL handle", who);
+  HILO_REFUSE_TIME_VARIANT(kf, who);
   if (!kf->discrete && kf->kp.continuous)
     return fail(HILO_ENOTSUP, "%s: the handle holds a continuous model that was not discretised; the Jacobians and gains here are those "
                               "of the discrete-time map (Model.discretize)", who);

@@ -72,6 +72,22 @@ template <class M> struct ModelSym { static constexpr bool value = false, HAS_ME
 template <class M, class = void> struct model_has_ext : bool_const<false> {};
 template <class M> struct model_has_ext<M, void_tt<decltype(M::EXT)>> : bool_const<M::EXT> {};
 
+// A time-variant model (dx/dt = f(t, x, u, p), y = h(t, x, u, p)) declares `static constexpr bool TIME_VARIANT = true` and, next to
+// `ode` / `meas`, `ode_t` / `meas_t` with the time as their first argument; a functor without the declaration is autonomous.
+// Time reaches a functor in the roll-out (hilo_integrate.h) and the maps below only.
+template <class M, class = void> struct model_time_variant : bool_const<false> {};
+template <class M> struct model_time_variant<M, void_tt<decltype(M::TIME_VARIANT)>> : bool_const<M::TIME_VARIANT> {};
+template <class M, class T, class U, class P>
+HD void model_ode_at(double t, const T* x, const U* u, const P* p, double dt, T* dx) {
+  if constexpr (model_time_variant<M>::value) M::ode_t(t, x, u, p, dt, dx);
+  else M::ode(x, u, p, dt, dx);
+}
+template <class M, class T, class U, class P>
+HD void model_meas_at(double t, const T* x, const U* u, const P* p, double dt, T* y) {
+  if constexpr (model_time_variant<M>::value) M::meas_t(t, x, u, p, dt, y);
+  else M::meas(x, u, p, dt, y);
+}
+
 // one kernel term: k = alpha exp(-1/2 (M0 d0^2 + M1 d1^2)) and its contributions to value / gradient / Hessian
 template <int ORDER>
 __device__ __forceinline__ void gp2_term(double x0, double x1, double al, double M0, double M1, double s, double i, double* acc) {
@@ -602,8 +618,17 @@ template <int I> HD double erk_b(int order) {
   else return order == 4 ? 1.0 / 6 : 0.0;
 }
 
+// the nodes c_i = sum_j a_ij: (0), (0, 1/2), (0, 1/2, 1), (0, 1/2, 1/2, 1) for orders 1 to 4
+template <int I> HD double erk_c(int order) {
+  if constexpr (I == 0) return 0.0;
+  else if constexpr (I == 1) return 0.5;
+  else if constexpr (I == 2) return order == 3 ? 1.0 : 0.5;
+  else return 1.0;
+}
+
+// `ts`: the time at which the step starts; read by a time-variant functor only (stage I is evaluated at ts + c_I h)
 template <class M, int I, class T, class U, class P, class E>
-HD void erk_stage(int order, const T* x, const U* u, const P* p, double h, T (*k)[M::NX], const E& ext) {
+HD void erk_stage(int order, const T* x, const U* u, const P* p, double h, T (*k)[M::NX], const E& ext, double ts = 0.0) {
   constexpr int NX = M::NX;
   if (I < order) {
     T xi[NX];
@@ -616,6 +641,7 @@ HD void erk_stage(int order, const T* x, const U* u, const P* p, double h, T (*k
       xi[s] = acc;
     }
     if constexpr (model_has_ext<M>::value) M::ode(xi, u, p, h, k[I], ext);
+    else if constexpr (model_time_variant<M>::value) M::ode_t(ts + erk_c<I>(order) * h, xi, u, p, h, k[I]);
     else M::ode(xi, u, p, h, k[I]);
   } else {
 #pragma unroll
@@ -624,13 +650,13 @@ HD void erk_stage(int order, const T* x, const U* u, const P* p, double h, T (*k
 }
 
 template <class M, class T, class U, class P, class E>
-HD void erk_step(int order, const T* x, const U* u, const P* p, double h, T* xn, const E& ext) {
+HD void erk_step(int order, const T* x, const U* u, const P* p, double h, T* xn, const E& ext, double ts = 0.0) {
   constexpr int NX = M::NX;
   T k[4][NX];
-  erk_stage<M, 0>(order, x, u, p, h, k, ext);
-  erk_stage<M, 1>(order, x, u, p, h, k, ext);
-  erk_stage<M, 2>(order, x, u, p, h, k, ext);
-  erk_stage<M, 3>(order, x, u, p, h, k, ext);
+  erk_stage<M, 0>(order, x, u, p, h, k, ext, ts);
+  erk_stage<M, 1>(order, x, u, p, h, k, ext, ts);
+  erk_stage<M, 2>(order, x, u, p, h, k, ext, ts);
+  erk_stage<M, 3>(order, x, u, p, h, k, ext, ts);
 #pragma unroll
   for (int s = 0; s < NX; ++s)
     xn[s] = x[s] + (h * erk_b<0>(order)) * k[0][s] + (h * erk_b<1>(order)) * k[1][s] +
@@ -642,41 +668,45 @@ HD void erk_step(int order, const T* x, const U* u, const P* p, double h, T* xn,
 // fp64 arithmetic may not drop and that keep every earlier slope alive).  Same results as erk_step<M>(4, ...), a third of its live
 // values: with forward-mode types (Dual<N>, Jet2) the four slopes are most of a kernel's registers.
 template <class M, class T, class U, class P, class E>
-HD void rk4_classic(const T* x, const U* u, const P* p, double h, T* xn, const E& ext) {
+HD void rk4_classic(const T* x, const U* u, const P* p, double h, T* xn, const E& ext, double ts = 0.0) {
   constexpr int NX = M::NX;
   T k[NX], xi[NX], acc[NX];
-  auto f = [&](const T* at) {
+  auto f = [&](const T* at, double c) {
     if constexpr (model_has_ext<M>::value) M::ode(at, u, p, h, k, ext);
+    else if constexpr (model_time_variant<M>::value) M::ode_t(ts + c * h, at, u, p, h, k);
     else M::ode(at, u, p, h, k);
+    (void)c;
   };
-  f(x);
+  f(x, 0.0);
 #pragma unroll
   for (int s = 0; s < NX; ++s) { acc[s] = x[s] + (h * (1.0 / 6)) * k[s]; xi[s] = x[s] + (h * 0.5) * k[s]; }
-  f(xi);
+  f(xi, 0.5);
 #pragma unroll
   for (int s = 0; s < NX; ++s) { acc[s] = acc[s] + (h * (1.0 / 3)) * k[s]; xi[s] = x[s] + (h * 0.5) * k[s]; }
-  f(xi);
+  f(xi, 0.5);
 #pragma unroll
   for (int s = 0; s < NX; ++s) { acc[s] = acc[s] + (h * (1.0 / 3)) * k[s]; xi[s] = x[s] + (h * 1.0) * k[s]; }
-  f(xi);
+  f(xi, 1.0);
 #pragma unroll
   for (int s = 0; s < NX; ++s) xn[s] = acc[s] + (h * (1.0 / 6)) * k[s];
 }
 
 // one sampling interval of the shooting map: discrete models are evaluated directly (mpc.py:1381-1389,:1665),
-// continuous ones through ERK of the requested order with `nsub` equal sub-steps
+// continuous ones through ERK of the requested order with `nsub` equal sub-steps.  `t`: the time at which the interval starts, read
+// by a time-variant functor only - a discrete one is evaluated at t, sub-step `it` of a continuous one starts at t + it h
 template <class M, class T, class U, class P, class E = NoExt>
-HD void model_step(int order, int nsub, const T* x, const U* u, const P* p, double dt, T* xn, const E& ext = E()) {
+HD void model_step(int order, int nsub, const T* x, const U* u, const P* p, double dt, T* xn, const E& ext = E(), double t = 0.0) {
   if constexpr (M::DISCRETE) {
     if constexpr (model_has_ext<M>::value) M::ode(x, u, p, dt, xn, ext);
+    else if constexpr (model_time_variant<M>::value) M::ode_t(t, x, u, p, dt, xn);
     else M::ode(x, u, p, dt, xn);
   } else {
     constexpr int NX = M::NX;
     if (order == 4 && nsub == 1) {  // the common recipe `model.discretize('rk4')`
 #ifdef HILO_RK4_GENERIC               // developer builds: the generic map with the tableau folded at compile time
-      erk_step<M>(4, x, u, p, dt, xn, ext);
+      erk_step<M>(4, x, u, p, dt, xn, ext, t);
 #else
-      rk4_classic<M>(x, u, p, dt, xn, ext);
+      rk4_classic<M>(x, u, p, dt, xn, ext, t);
 #endif
       return;
     }
@@ -686,7 +716,8 @@ HD void model_step(int order, int nsub, const T* x, const U* u, const P* p, doub
     for (int s = 0; s < NX; ++s) xc[s] = x[s];
     for (int it = 0; it < nsub; ++it) {
       T xt[NX];
-      erk_step<M>(order, xc, u, p, h, xt, ext);
+      if constexpr (model_time_variant<M>::value) erk_step<M>(order, xc, u, p, h, xt, ext, t + it * h);
+      else erk_step<M>(order, xc, u, p, h, xt, ext);
 #pragma unroll
       for (int s = 0; s < NX; ++s) xc[s] = xt[s];
     }

@@ -2,7 +2,9 @@
 // csrc/hilo_integrate.h).
 //
 // Reference semantics: `Model.simulate` (hilo_mpc/modules/dynamic_model/dynamic_model.py:3911-4000) - inputs held over a
-// sampling interval, the state and the measurements recorded at every sampling instant - for a batch of instances.
+// sampling interval, the state and the measurements recorded at every sampling instant - for a batch of instances.  A run-time
+// compiled model may depend on time explicitly (hilo_integrate.h, the section on time): its kernels take the time of the first
+// row as a trailing argument; the functors of the zoo are autonomous and their kernels are the ones they were.
 #include "hilo_integrate.h"
 #include "hilo_kf_handle.h"
 
@@ -53,12 +55,13 @@ static_assert(HILO_SIM_DOPRI5_MAX_NX == DOPRI5_MAX_NX && HILO_SIM_DOPRI5 == SIM_
               HILO_SIM_STATUS_STEP_TOO_SMALL == SIM_STEP_TOO_SMALL && HILO_SIM_BDF == SIM_BDF && HILO_SIM_BDF_MAX_NX == BDF_MAX_NX,
               "include/hilo_hip.h and csrc/hilo_integrate.h disagree");
 
-extern "C" int hilo_model_rollout(hilo_kf* kf, const hilo_sim_opts* opts, int64_t batch, int steps, const double* x0,
-                                  const double* up, int64_t up_stride, int64_t up_step, double* X, double* Y, int32_t* stats,
-                                  void* stream) {
+// hilo_model_rollout (h NULL) and hilo_model_rollout_resume
+static int rollout_impl(hilo_kf* kf, const hilo_sim_opts* opts, int64_t batch, int steps, const double* x0, const double* up,
+                        int64_t up_stride, int64_t up_step, double* X, double* Y, int32_t* stats, double* h, void* stream) {
   HILO_REQUIRE(kf, "hilo_model_rollout: NULL handle");
   HILO_REQUIRE(batch >= 0 && steps >= 1, "hilo_model_rollout: need batch >= 0 and steps >= 1");
   SimParams sp = {SIM_MAP, 10000, 1e-6, 1e-8, 0.0};
+  double t0 = 0.0;   // the time of row 0 of X (read by a time-variant model only)
   if (opts) {
     HILO_REQUIRE(opts->method == HILO_SIM_MAP || opts->method == HILO_SIM_DOPRI5 || opts->method == HILO_SIM_BDF,
                  "hilo_model_rollout: unknown method %d", opts->method);
@@ -67,6 +70,8 @@ extern "C" int hilo_model_rollout(hilo_kf* kf, const hilo_sim_opts* opts, int64_
     if (opts->rtol > 0.0) sp.rtol = opts->rtol;
     if (opts->atol > 0.0) sp.atol = opts->atol;
     if (opts->h0 > 0.0) sp.h0 = opts->h0;
+    HILO_REQUIRE(opts->t0 == opts->t0 && ::fabs(opts->t0) < INFINITY, "hilo_model_rollout: t0 must be finite");
+    t0 = opts->t0;
   }
   if (sp.method == SIM_DOPRI5) {
     if (kf->discrete || !kf->kp.continuous)
@@ -90,6 +95,10 @@ extern "C" int hilo_model_rollout(hilo_kf* kf, const hilo_sim_opts* opts, int64_
       return fail(HILO_ENOTSUP, "hilo_model_rollout: the compiled right-hand side of this model leaves HILO_SIM_BDF %d bytes of scratch "
                                 "memory per lane; the method is built to keep its vectors in registers", kf->jit.rollout_bdf_scratch);
   }
+  if (sp.method != SIM_DOPRI5) h = nullptr;   // the other methods have no proposal to hand on
+  if (h && kf->desc.model_id != 100 /* HILO_MODEL_USER */)
+    return fail(HILO_ENOTSUP, "hilo_model_rollout_resume: the step-size proposal is handed on by the kernels of a run-time compiled "
+                              "model; this handle holds a model of the zoo (pass h = NULL)");
   if (batch == 0) return HILO_OK;
   HILO_REQUIRE(x0 && X, "hilo_model_rollout: NULL argument");
   HILO_REQUIRE(kf->nu + kf->np == 0 || up, "hilo_model_rollout: the model has %d inputs/parameters but `up` is NULL", kf->nu + kf->np);
@@ -106,7 +115,7 @@ extern "C" int hilo_model_rollout(hilo_kf* kf, const hilo_sim_opts* opts, int64_
     hipFunction_t fn = sp.method == SIM_BDF ? kf->jit.rollout_bdf : kf->jit.rollout;
     HILO_REQUIRE(fn, "hilo_model_rollout: the run-time compiled roll-out kernel is not loaded");
     KfParams kpv = kp;
-    void* args[] = {&kpv, &sp, &batch, &steps, &x0, &up, &up_stride, &up_step, &X, &Y, &st};
+    void* args[] = {&kpv, &sp, &batch, &steps, &x0, &up, &up_stride, &up_step, &X, &Y, &st, &t0, &h};   // (h: hilo_user_rollout alone)
     const unsigned grid = (unsigned)((batch + ROLLOUT_TPB - 1) / ROLLOUT_TPB);
     HILO_HIP_CHECK(hipModuleLaunchKernel(fn, grid, 1, 1, ROLLOUT_TPB, 1, 1, 0, s, args, nullptr));
     return HILO_OK;
@@ -121,4 +130,16 @@ extern "C" int hilo_model_rollout(hilo_kf* kf, const hilo_sim_opts* opts, int64_
       return rollout_launch<Lti<4, 2, 2>>(kp, sp, batch, steps, x0, up, up_stride, up_step, X, Y, st, s);
   }
   return fail(HILO_EINVAL, "unknown model id %d", kf->desc.model_id);
+}
+
+extern "C" int hilo_model_rollout(hilo_kf* kf, const hilo_sim_opts* opts, int64_t batch, int steps, const double* x0,
+                                  const double* up, int64_t up_stride, int64_t up_step, double* X, double* Y, int32_t* stats,
+                                  void* stream) {
+  return rollout_impl(kf, opts, batch, steps, x0, up, up_stride, up_step, X, Y, stats, nullptr, stream);
+}
+
+extern "C" int hilo_model_rollout_resume(hilo_kf* kf, const hilo_sim_opts* opts, int64_t batch, int steps, const double* x0,
+                                         const double* up, int64_t up_stride, int64_t up_step, double* X, double* Y,
+                                         int32_t* stats, double* h, void* stream) {
+  return rollout_impl(kf, opts, batch, steps, x0, up, up_stride, up_step, X, Y, stats, h, stream);
 }

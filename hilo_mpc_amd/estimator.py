@@ -70,7 +70,9 @@ class _KalmanFilter:
     _type = None
 
     def __init__(self, model, id=None, name=None, plot_backend=None, square_root_form=True, device_index=None,
-                 n_sub=None):
+                 n_sub=None, _as_plant=False):
+        if not _as_plant:           # (Model._plant_handle: the handle only carries the plant's functor to hilo_model_rollout)
+            model._refuse_time_variant(self._type or 'estimator')
         if not model._is_setup:                                   # estimator/base.py:74-76
             raise RuntimeError(f"Model is not set up. Run Model.setup() before passing it to the "
                                f"{'Kalman filter' if 'Kalman' in (self._type or '') else self._type}.")

@@ -22,6 +22,7 @@ class LMPC:
 
     def __init__(self, model, id=None, name=None, plot_backend=None, device_index=None):
         sym = getattr(model, '_symbolic', False)
+        model._refuse_time_variant('LMPC')
         if model.name != 'lti' and not model.is_linear():
             raise TypeError("The model is nonlinear. Use the NMPC class or linearize the model.")
         if model.name != 'lti' and not sym:

@@ -63,6 +63,7 @@ class LinearQuadraticRegulator:
     def __init__(self, model, id=None, name=None, discrete=True, plot_backend=None, device_index=None):
         if not isinstance(model, Model):
             raise TypeError("The model must be an object of the Model class.")
+        model._refuse_time_variant('LQR')
         if not model._is_setup:
             raise RuntimeError("Model is not set up. Run Model.setup() before passing it to the controller.")
         if discrete and not model.discrete:

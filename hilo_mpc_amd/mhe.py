@@ -106,6 +106,7 @@ class _StageCost:
 
 class MovingHorizonEstimator:
     def __init__(self, model, id=None, name=None, plot_backend=None, time=0., device_index=None):
+        model._refuse_time_variant('MHE')
         if not model._is_setup:
             model.setup()
         self._model = model                          # continuous: collocation by default, like the reference (mhe.py:512)

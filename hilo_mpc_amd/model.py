@@ -113,6 +113,8 @@ class Model:
     u = property(lambda s: SymVector('u', s.input_names))
     p = property(lambda s: SymVector('p', s.parameter_names))
     z = property(lambda s: SymVector('z', getattr(s, 'algebraic_state_names', [])))
+    t = property(lambda s: Expr('t', name='t'))     # the time, for equations written as expressions (`u[0] * sin(w * m.t)`)
+    time = t
 
     @property
     def discrete(self):
@@ -171,6 +173,7 @@ class Model:
         from .parsing import FUNCTIONS
         ns = dict(FUNCTIONS)                        # the reference's function table (util/parsing.py:36-58)
         ns['dt'] = Expr('dt', name='dt')            # the sampling interval inside the equations of a discrete model
+        ns['t'] = Expr('t', name='t')               # the time: a time-variant model (is_time_variant)
         for vec in (self.x, self.u, self.p, self.z):
             ns.update({n: vec[n] for n in vec._names})
         out = []
@@ -249,6 +252,23 @@ class Model:
             return False
         return not any(n.op in ('x', 'z', 'u') for r in J for e in r for n in e.nodes().values())
 
+    def is_time_variant(self):
+        """dynamic_model.py:2480-2486: an equation names the time t explicitly.  Such a model is simulated as a plant (`step`,
+        `rollout`, `simulate`, the plant of a `SimpleControlLoop`); controllers, estimators and the linearisations refuse it."""
+        if not self._symbolic or self._ode is None:
+            return False
+        return any(e.depends_on('t') for e in list(self._ode) + list(self._meas) + list(self._alg))
+
+    def is_autonomous(self):
+        """dynamic_model.py:2458-2463: the model has no inputs (the reference's meaning of the word; time dependence is
+        `is_time_variant`)."""
+        return self.n_u == 0
+
+    def _refuse_time_variant(self, who, instead="simulate it as a plant (Model.step, rollout, simulate, the plant of a SimpleControlLoop)"):
+        if self.is_time_variant():
+            raise NotImplementedError(f"model '{self.name}' depends on time explicitly; {who} takes autonomous models only: write the "
+                                      f"time dependence as an input or a time-varying parameter of the {who} model, or {instead}")
+
     def user_source(self, z_guess=None, alg_at_slope=False):
         """HIP source that defines `UserModel` for the run-time compiled path: the emitted functor, or the alias of the
         zoo functor.  z_guess: start of the Newton iteration on the algebraic equations of a DAE (`set_initial_guess(z_guess=)`)."""
@@ -322,6 +342,7 @@ class Model:
                 print("Model is already linear. Linearization is not necessary. Nothing to be done.")
                 return self
             raise NotImplementedError("the models of the device zoo carry no expressions to linearise")
+        self._refuse_time_variant('linearize')
         if trajectory is not None:
             raise NotImplementedError("linearisation along a trajectory is not built")
         if self._ode is None:
@@ -368,7 +389,8 @@ class Model:
         fx = SMPC._discrete_map(self, self.dt) if self.discrete else list(self._ode)
         rows = list(fx) + list(self._meas)
         if any(e.depends_on('t') for e in rows):
-            raise NotImplementedError("system matrices of a model that depends on time explicitly")
+            raise NotImplementedError(f"model '{self.name}' depends on time explicitly; system matrices are those of autonomous models: "
+                                      f"write the time dependence as an input or a parameter, or simulate the model as a plant")
         if any(e.depends_on('dt') for e in rows):      # the sampling interval written into the equations (tests/test_LMPC.py:12-13)
             if self.dt is None:
                 raise RuntimeError("Model is not set up. Run Model.setup(dt=...) first: the equations hold the sampling interval.")
@@ -454,6 +476,7 @@ class Model:
         import torch
         from . import _lib
         from ._device import ptr, stream_ptr, to_dev
+        self._refuse_time_variant('linearization')
         if not self._is_setup:
             raise RuntimeError("Model is not set up. Run Model.setup() before asking for its linearisation.")
         if not self.discrete:
@@ -539,6 +562,10 @@ class Model:
         (attempted steps per sampling interval), first_step 0 (estimated)."""
         if self._symbolic and self._ode is None:
             raise RuntimeError("Model is not set up: no dynamical equations (set_dynamical_equations)")
+        if getattr(self, 'n_z', 0) and self.is_time_variant():
+            raise NotImplementedError(f"model '{self.name}' has algebraic states and depends on time explicitly: time-variant models are "
+                                      f"ordinary differential (or difference) equations; eliminate the algebraic states or write the "
+                                      f"time dependence as an input")
         if solver is None and solver_options is not None:
             raise ValueError("solver_options without a solver")
         if solver is not None:
@@ -766,21 +793,22 @@ class Model:
             import warnings
             with warnings.catch_warnings():
                 warnings.simplefilter('ignore')
-                h = ExtendedKalmanFilter(self, device_index=device_index)
+                h = ExtendedKalmanFilter(self, device_index=device_index, _as_plant=True)
             h.setup()
             h._model_stamp = (self.dt, self.erk_order, self.n_sub, id(self._ode) if self._symbolic else None)
             self._plant = h
         return h
 
-    def step(self, x, u=None, p=None, device_index=None):
-        """x [B, n_x] -> (x_next [B, n_x], y [B, n_y]) after one sampling interval, on the device (numpy in -> numpy out)."""
+    def step(self, x, u=None, p=None, device_index=None, t0=0.):
+        """x [B, n_x] -> (x_next [B, n_x], y [B, n_y]) after one sampling interval, on the device (numpy in -> numpy out).
+        t0: the time at which the interval starts, one value for the batch (read by a time-variant model only)."""
         import torch
         from . import _lib
         from ._device import ptr, stream_ptr, to_dev
         if not self._is_setup:
             raise RuntimeError("Model is not set up. Run Model.setup() before running simulations.")
-        if self._solver is not None:          # one sampling interval under error control
-            xs, ys = self.rollout(x, u, p, steps=1, device_index=device_index)
+        if self._solver is not None or self.is_time_variant():   # one sampling interval under error control / with the time
+            xs, ys = self.rollout(x, u, p, steps=1, device_index=device_index, t0=t0)
             return xs[1], ys[0]
         h = self._plant_handle(device_index)
         dev = h._dev
@@ -808,7 +836,7 @@ class Model:
         xn, y = xn[:, 0], y[:, 0]
         return (xn.cpu().numpy(), y.cpu().numpy()) if host else (xn, y)
 
-    def rollout(self, x0, u=None, p=None, steps=1, return_stats=False, device_index=None):
+    def rollout(self, x0, u=None, p=None, steps=1, return_stats=False, device_index=None, t0=0., _h=None):
         """The many-interval sibling of `step`: `steps` sampling intervals for a batch of states in ONE launch
         (`hilo_model_rollout`), with the model's own map or, after `setup(solver='dopri5')` or `'bdf'`, under error control.
 
@@ -818,7 +846,16 @@ class Model:
         'status' (0 ok, 1 max_num_steps reached, 2 step size too small), 'n_accepted', 'n_rejected', 'n_rhs'.  The rows of an instance
         whose integration failed are NaN from the sampling instant it did not reach.  Allocates its outputs; inputs AND
         parameters together are packed into one buffer that is kept for the next call - calls on one model must therefore be
-        ordered on one stream (the current stream of the device at the time of the call): a second call rewrites the buffer."""
+        ordered on one stream (the current stream of the device at the time of the call): a second call rewrites the buffer.
+
+        t0: the time of x0, one value for the batch (a per-instance phase belongs in a parameter); read by a time-variant model only.
+        Sampling interval k starts at t_k = t0 + k dt.  Over it a continuous model's right-hand side is f(t_k + tau, x, u[k], p),
+        tau in [0, dt] - the inputs are held, time is not - and y[k] = h(t_k + dt, x[k + 1], u[k], p); a discrete model's map and
+        measurement both see t_k: x[k + 1] = f(t_k, x[k], u[k], p), y[k] = h(t_k, x[k + 1], u[k], p).
+
+        _h (what `simulate` keeps between its calls): a one-element list holding the 'dopri5' step-size proposals [B] that the previous
+        roll-out ended with (None: none yet); they are this one's first steps and are replaced by the ones it ends with
+        (`hilo_model_rollout_resume`)."""
         import ctypes
         import torch
         from . import _lib
@@ -864,12 +901,19 @@ class Model:
         Y = torch.empty(steps, B, ny, dtype=torch.float64, device=dev)
         stats = torch.empty(B, 4, dtype=torch.int32, device=dev) if return_stats else None
         opts = _lib.SimOpts()
+        opts.t0 = float(t0)
         if self._solver is not None:
             o = self._solver_options
             opts.method, opts.max_steps = SOLVERS[self._solver], o['max_num_steps']
             opts.rtol, opts.atol, opts.h0 = o['reltol'], o['abstol'], o['first_step']
-        _lib.check(_lib.lib().hilo_model_rollout(h._handle, ctypes.byref(opts), B, steps, ptr(xt), ptr(up), up_stride, up_step, ptr(X),
-                                                 ptr(Y), ptr(stats), stream_ptr(dev)))
+        if _h is not None and self._solver == 'dopri5':
+            if _h[0] is None or _h[0].shape != (B,) or _h[0].device != xt.device:
+                _h[0] = torch.zeros(B, dtype=torch.float64, device=dev)
+            _lib.check(_lib.lib().hilo_model_rollout_resume(h._handle, ctypes.byref(opts), B, steps, ptr(xt), ptr(up), up_stride, up_step,
+                                                            ptr(X), ptr(Y), ptr(stats), ptr(_h[0]), stream_ptr(dev)))
+        else:
+            _lib.check(_lib.lib().hilo_model_rollout(h._handle, ctypes.byref(opts), B, steps, ptr(xt), ptr(up), up_stride, up_step, ptr(X),
+                                                     ptr(Y), ptr(stats), stream_ptr(dev)))
         out = (X.cpu().numpy(), Y.cpu().numpy()) if host else (X, Y)
         if return_stats:
             st = stats.cpu().numpy() if host else stats
@@ -892,7 +936,9 @@ class Model:
         """dynamic_model.py:3911-4000: advance the stored state by `steps` sampling intervals (or up to `tf`: int(tf / dt) of them,
         :3937-3941 - truncated, so a `tf` that floating-point division leaves just below a multiple of dt loses an interval, and tf < dt
         does nothing) with the inputs held; results in `model.solution` (`solution['x:f']` the last state, `solution['x']` the
-        trajectory).  Without a solver and with inputs / parameters of at most two dimensions this is a loop over `step`.  With
+        trajectory).  A time-variant model starts each call at `solution['t:f']` (`set_initial_conditions(x0, t0)` sets the first)
+        and is always ONE `rollout`; under 'dopri5' it also starts with the step sizes the last call ended with, so that calls in a row
+        give what one `rollout` over all of them gives.  Without a solver and with inputs / parameters of at most two dimensions this is a loop over `step`.  With
         `setup(solver=...)`, or with a sequence u [steps, B, n_u] (p likewise; `steps` is then taken from it), it is ONE `rollout`;
         `solution['status']`, `['n_accepted']`, `['n_rejected']` hold the integrator's per-instance status and step counts of each
         call."""
@@ -905,14 +951,17 @@ class Model:
         if int(steps) == 0 and not [v for v in (u, p) if v is not None and getattr(v, 'ndim', np.ndim(v)) == 3]:
             return                                # (tf < dt: nothing to do, on either path)
         seq = [v for v in (u, p) if v is not None and getattr(v, 'ndim', np.ndim(v)) == 3]
-        if self._solver is not None or seq:
+        if self._solver is not None or seq or self.is_time_variant():
             for v in seq:
                 steps = int(v.shape[0] if hasattr(v, 'shape') else len(v))
             host = lambda v: None if v is None else np.asarray(v.cpu() if hasattr(v, 'cpu') else v, dtype=float)
             u, p = host(u), host(p)
             if u is not None and u.ndim < 3:
                 u = u.reshape(1, -1) if u.size == self.n_u else (u.T if u.ndim == 2 and u.shape[0] == self.n_u and u.shape[1] != self.n_u else u)
-            x, y, st = self.rollout(self._sim['x'][-1], u, p, steps=steps, return_stats=True)
+            # a time-variant model goes on with the step sizes of its last call: two calls equal one roll-out over both stretches
+            # (an autonomous model's calls each estimate their first step, as they always did)
+            keep = self._sim.setdefault('_h', [None]) if self.is_time_variant() else None
+            x, y, st = self.rollout(self._sim['x'][-1], u, p, steps=steps, return_stats=True, t0=self._sim['t'][-1], _h=keep)
             for k in range(int(steps)):
                 self._sim['x'].append(x[k + 1]), self._sim['y'].append(y[k])
                 self._sim['u'].append(u if u is None or u.ndim < 3 else u[k])

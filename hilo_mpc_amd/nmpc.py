@@ -347,6 +347,7 @@ class NMPC:
     def __init__(self, model, id=None, name=None, plot_backend=None, use_sx=True, stats=False, device_index=None):
         # a continuous model is transcribed at setup() by `integration_method`: 'collocation' (the reference's default,
         # optimizer.py:1410-1418) or explicit Runge-Kutta ('rk4' / 'erk'); a discrete(-ised) model uses 'discrete'
+        model._refuse_time_variant(getattr(self, 'type', None) or 'NMPC')
         if not model._is_setup:
             model.setup()
         self._model = model

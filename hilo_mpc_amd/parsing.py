@@ -13,6 +13,7 @@
 Variables that are not declared elsewhere are recognised by their time argument: `name(t)` on a right-hand side is an algebraic
 state, `name(k)` an input (piecewise constant), every other free identifier a parameter - in the order of their first
 appearance (differential equations first, then algebraic, then measurement equations, like the reference processes them).
+A bare `t` is the time: the model is time-variant (periodic forcing, a scheduled disturbance, a clock-driven reference).
 `^` is the power operator.  The result is expression trees (hilo_mpc_amd/expr.py), evaluated with Python's own parser on a
 namespace of the model's symbols.
 """
@@ -153,7 +154,7 @@ def parse_dynamic_equations(equations, discrete=False, x=(), y=(), z=(), u=(), p
             elif name == 'dt':
                 ns[name] = symbols['dt']
             elif name == 't':
-                raise NotImplementedError("explicitly time-dependent model equations are not offloaded")
+                ns[name] = symbols['t']
             else:
                 for kind, pool in (('x', m.x), ('z', m.z), ('u', m.u), ('p', m.p)):
                     if name in pool:
@@ -170,6 +171,8 @@ def parse_dynamic_equations(equations, discrete=False, x=(), y=(), z=(), u=(), p
         def __missing__(self, key):
             if key == 'dt':
                 v = Expr('dt', name='dt')
+            elif key == 't':
+                v = Expr('t', name='t')      # the time itself (`sin(w*t)`): a time-variant model (Model.is_time_variant)
             else:
                 kind, name = key
                 pool = {'x': m.x, 'z': m.z, 'u': m.u, 'p': m.p}[kind]

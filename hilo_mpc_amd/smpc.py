@@ -96,6 +96,7 @@ class SMPC(NMPC):
 
     def __init__(self, det_model, stoch_model, B, id=None, name=None, plot_backend=None, use_sx=True, stats=False, Kgain=None,
                  device_index=None):
+        det_model._refuse_time_variant('SMPC')
         self._n_x_s, self._n_u_s, self._n_p_s = det_model.n_x, det_model.n_u, det_model.n_p
         self._n_y_s, self._n_z_s = det_model.n_y, getattr(det_model, 'n_z', 0)
         self._Kgain_is_set = Kgain is not None

@@ -189,7 +189,16 @@ int hilo_kf_steps_split(hilo_kf* kf, int64_t batch, int steps, const double* xP,
    An instance whose integration fails - more than max_steps attempted steps within ONE sampling interval
    (HILO_SIM_STATUS_MAX_STEPS; HILO_SIM_BDF: between two consecutive sampling instants), or a step below 16 eps |t| (HILO_SIM_BDF: ten
    spacings of t) (HILO_SIM_STATUS_STEP_TOO_SMALL) - ends with that status, and its rows
-   from the sampling instant it did not reach onwards are NaN; the other instances are not affected and the call returns HILO_OK. */
+   from the sampling instant it did not reach onwards are NaN; the other instances are not affected and the call returns HILO_OK.
+   Time.  A run-time compiled model may name the time t in its equations (a functor that declares TIME_VARIANT).  opts->t0 (NULL
+   opts: 0) is the time of row 0 of X, one value for the batch; sampling interval k starts at t_k = t0 + k dt.  Over the interval a
+   continuous model's right-hand side is f(t_k + tau, x, u_k, p), tau in [0, dt] - the inputs are held, time is not: stage i of a
+   Runge-Kutta sub-step of length h that starts at s is evaluated at s + c_i h, HILO_SIM_DOPRI5 uses the stage times of scipy's RK45,
+   HILO_SIM_BDF evaluates fun(t_new, y) and the Jacobian df/dx at the current (t, x), with inputs held on the clock of its one
+   integration plus t0, with an input sequence restarted at every t_k - and Y[k] = h(t_k + dt, x_{k+1}, u_k, p).  A discrete model's
+   map and measurement of interval k both see t_k: x_{k+1} = f(t_k, x_k, u_k, p), Y[k] = h(t_k, x_{k+1}, u_k, p).  The smallest
+   admissible step is measured against the absolute time.  Every other entry that takes a filter handle - hilo_kf_*,
+   hilo_pf_function, hilo_model_linearize, hilo_lqr_call - returns HILO_ENOTSUP for a time-variant model. */
 #define HILO_SIM_MAP 0
 #define HILO_SIM_DOPRI5 1
 #define HILO_SIM_DOPRI5_MAX_NX 12
@@ -203,10 +212,21 @@ typedef struct hilo_sim_opts {
   int32_t max_steps;  /* attempted steps per sampling interval (<= 0: 10000) */
   double rtol, atol;  /* <= 0: 1e-6, 1e-8 */
   double h0;          /* first step (<= 0: estimated) */
+  double t0;          /* time of row 0 of X, one value for the batch (read by a time-variant model only) */
 } hilo_sim_opts;
 int hilo_model_rollout(hilo_kf* kf, const hilo_sim_opts* opts, int64_t batch, int steps, const double* x0,
                        const double* up, int64_t up_stride, int64_t up_step, double* X, double* Y, int32_t* stats,
                        void* stream);
+/* The same roll-out as one piece of a longer one.  h [B] (device) or NULL: the step-size proposal of HILO_SIM_DOPRI5 per instance -
+   an entry > 0 is the first step that instance tries (any other: opts->h0, or the estimate), and every entry is overwritten with
+   the proposal the instance ended with.  Inputs unchanged, a second call that starts from the last row of X, at the time
+   t0 + steps dt, with the h the first call left takes the steps ONE call over both stretches would have taken: the proposal
+   is all the pair carries across a sampling instant (the slope at the start is evaluated again, at the same time and state).
+   The other methods ignore h.  HILO_ENOTSUP for a non-NULL h with HILO_SIM_DOPRI5 on a model of the zoo: the run-time compiled
+   kernels alone hand the proposal on. */
+int hilo_model_rollout_resume(hilo_kf* kf, const hilo_sim_opts* opts, int64_t batch, int steps, const double* x0,
+                              const double* up, int64_t up_stride, int64_t up_step, double* X, double* Y, int32_t* stats,
+                              double* h, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------- */
 /* Linear-quadratic regulator: batched linearisation, Riccati gains and feedback                            */

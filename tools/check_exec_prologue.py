@@ -10,7 +10,8 @@ no lane and the value read back later is garbage.  It cost this project the filt
     python tools/check_exec_prologue.py [libhilo_hip.so]
 
 disassembles every gfx950 code object of the library and reports join blocks entered with EXEC == 0 whose code before the
-`s_or_b64 exec` consists of scalar / lane instructions and at least one vector copy or spill.  Exit status 1 when there are any."""
+`s_or_b64 exec` (or the saveexec instruction that opens an else-region, ELSE_ENTRY below) consists of scalar / lane instructions
+and at least one vector copy or spill.  Exit status 1 when there are any."""
 import os
 import re
 import struct
@@ -22,6 +23,11 @@ OBJDUMP = '/opt/rocm/lib/llvm/bin/llvm-objdump'
 OBJCOPY = '/opt/rocm/lib/llvm/bin/llvm-objcopy'
 MAGIC = b'__CLANG_OFFLOAD_BUNDLE__'
 LANE_OPS = ('v_writelane', 'v_readlane', 'v_readfirstlane')      # do not depend on EXEC
+# The head of an else-region: `s_andn2_saveexec_b64 sD, sS` sets EXEC = sS & ~EXEC, `s_or_saveexec_b64` EXEC = sS | EXEC and
+# `s_xor_saveexec_b64` EXEC = sS ^ EXEC - entered with EXEC == 0 each of them enables the lanes of the saved mask sS, exactly like
+# the `s_or_b64 exec`.  What stands in front of it executes for no lane (reported), what follows it is the else-branch's own
+# code, executed by the lanes that take it.  (`s_and_saveexec_b64` leaves EXEC == 0 and is passed over like any scalar code.)
+ELSE_ENTRY = ('s_andn2_saveexec_b64', 's_or_saveexec_b64', 's_xor_saveexec_b64')
 COPY = re.compile(r'^(v_mov_b32|v_mov_b64|v_accvgpr_write|v_accvgpr_read|v_accvgpr_mov|scratch_store|scratch_load)')
 
 
@@ -74,7 +80,7 @@ def check(elf):
     for k in sorted(s for s in starts if s is not None):
         bad = []
         for a, op, args, f in ins[k:k + 64]:
-            if op == 's_or_b64' and args.replace(' ', '').startswith('exec,exec,'):
+            if (op == 's_or_b64' and args.replace(' ', '').startswith('exec,exec,')) or op in ELSE_ENTRY:
                 if bad:
                     hits.append((ins[k][3], bad))         # only copies / spills / scalar code before the lanes come back
                 break
