@@ -90,8 +90,29 @@ template <int N> HD Dual<N> chain(const Dual<N>& a, double f, double df) {
 }
 // sine and cosine of one argument from ONE argument reduction (a model that names sin(psi) and cos(psi) asks for both twice in
 // derivative arithmetic: four reductions of ~100 instructions each per evaluation with the separate calls)
+// HILO_TRIG_CALLS (defined by the run-time compiled filter unit, csrc/hilo_jit.hip::jit_kf_kernels): the library's sine and cosine
+// behind a real call.  Their argument reduction branches per lane (the path for huge arguments); inlined into a filter kernel of
+// a model with five or more states the register allocator put the spills of the kernel's live values into the join block of that
+// branch, in front of its EXEC restore - executed for no lane when no lane takes the huge-argument path, the values read back
+// afterwards are garbage (filter results off by 1e-2 for n_x = 5..8, tests/test_kf_shapes_gpu.py).  Inside a
+// function of its own the branch sees only that function's few registers.
+#if defined(HILO_TRIG_CALLS) && defined(__HIP_DEVICE_COMPILE__)
+struct SinCos { double s, c; };
+__device__ __attribute__((noinline)) inline SinCos sin_cos_call(double x) { SinCos r; ::sincos(x, &r.s, &r.c); return r; }
+__device__ __attribute__((noinline)) inline double sin_call(double x) { return ::sin(x); }
+__device__ __attribute__((noinline)) inline double cos_call(double x) { return ::cos(x); }
+#define HILO_SIN(x) sin_call(x)
+#define HILO_COS(x) cos_call(x)
+#else
+#define HILO_SIN(x) ::sin(x)
+#define HILO_COS(x) ::cos(x)
+#endif
 HD void sin_cos(double x, double& s, double& c) {
-#if defined(__HIP_DEVICE_COMPILE__)
+#if defined(HILO_TRIG_CALLS) && defined(__HIP_DEVICE_COMPILE__)
+  const SinCos r = sin_cos_call(x);
+  s = r.s;
+  c = r.c;
+#elif defined(__HIP_DEVICE_COMPILE__)
   ::sincos(x, &s, &c);
 #else
   s = ::sin(x);
@@ -163,8 +184,8 @@ HD FastD operator*(FastD a, double c) { return FastD(a.v * c); }
 HD FastD operator*(double c, FastD a) { return FastD(c * a.v); }
 HD FastD operator/(FastD a, double c) { return FastD(a.v * (1.0 / c)); }
 HD FastD operator/(double c, FastD a) { return FastD(c * rcp_fast(a.v)); }
-HD FastD sin(FastD a) { return FastD(::sin(a.v)); }
-HD FastD cos(FastD a) { return FastD(::cos(a.v)); }
+HD FastD sin(FastD a) { return FastD(HILO_SIN(a.v)); }
+HD FastD cos(FastD a) { return FastD(HILO_COS(a.v)); }
 HD FastD exp(FastD a) { return FastD(::exp(a.v)); }
 HD FastD log(FastD a) { return FastD(::log(a.v)); }
 HD FastD sqrt(FastD a) { return FastD(::sqrt(a.v)); }
@@ -245,8 +266,8 @@ template <int N> HD double valof(const Dual<N>& v) { return v.v; }
 
 // plain doubles take part in the same generic code (explicit overloads: inside this namespace the AD
 // overloads would otherwise hide ::sin etc. and a double would convert silently to Jet2)
-HD double sin(double x) { return ::sin(x); }
-HD double cos(double x) { return ::cos(x); }
+HD double sin(double x) { return HILO_SIN(x); }
+HD double cos(double x) { return HILO_COS(x); }
 HD double exp(double x) { return ::exp(x); }
 HD double log(double x) { return ::log(x); }
 HD double sqrt(double x) { return ::sqrt(x); }

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "hilo_jit.h"
+#include "hilo_kf_params.h"
 #include "hilo_ocp.h"
 
 namespace hilo {
@@ -360,7 +361,18 @@ int jit_nmpc_kernels(const JitRequest& r, int device, JitKernels* out) {
 static std::map<std::string, JitKfKernels> g_kf_loaded;
 
 int jit_kf_kernels(const std::string& user_source, int device, JitKfKernels* out, bool compile_only, bool private_module) {
-  std::string tu = "#include \"hilo_kf_kernel.h\"\n#include \"hilo_integrate.h\"\n#include \"hilo_lqr.h\"\nextern \"C\" { __device__ const double* hilo_user_gp[4]; }\nnamespace hilo {\n";
+  {
+    // all filter kernels of a model share this unit, and the UKF's one-lane kernels stage 64 tiles of n_x (3 n_x + 2) doubles in
+    // static LDS (csrc/hilo_kf_kernel.h::kf_body): 160 KB are passed at n_x = 10 - refused here, not by the compiler's log
+    const char* tag = "static constexpr int NX = ";
+    const size_t at = user_source.find(tag);
+    const int nx = at == std::string::npos ? 0 : atoi(user_source.c_str() + at + strlen(tag));
+    if (nx > KF_MAX_NX)
+      return fail(HILO_EINVAL, "the filters (KF, EKF, UKF, PF) of a model written as expressions are built for up to %d states: the "
+                  "unscented filter's prediction tiles, 64 x n_x (3 n_x + 2) doubles, pass the 160 KB of LDS at n_x = 10 - the model has %d",
+                  KF_MAX_NX, nx);
+  }
+  std::string tu = "#define HILO_TRIG_CALLS 1\n#include \"hilo_kf_kernel.h\"\n#include \"hilo_integrate.h\"\n#include \"hilo_lqr.h\"\nextern \"C\" { __device__ const double* hilo_user_gp[4]; }\nnamespace hilo {\n";
   tu += user_source;
   tu += R"(
 }  // namespace hilo

@@ -456,6 +456,7 @@ __device__ __forceinline__ void kf_body(const KfParams& kp, int64_t batch, const
   constexpr int IN_ROW = (MODE == 1) ? PRED : XP;
   constexpr int OUT_ROW = (MODE == 0) ? PRED : XP;
   constexpr int BIG = IN_ROW > OUT_ROW ? IN_ROW : OUT_ROW;
+  static_assert(sizeof(double) * KF_TPB * TilePitch<BIG>::value <= 160 * 1024, "kf_body: the staged tiles exceed the LDS (NX <= KF_MAX_NX)");
   __shared__ double lds[KF_TPB * TilePitch<BIG>::value];
 
   // `ipw` instances per workgroup (<= KF_TPB): a small batch is spread over all compute units (16 instances per wave at the

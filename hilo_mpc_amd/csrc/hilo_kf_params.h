@@ -13,4 +13,8 @@ struct KfParams {
   long long pp_stride = 0;
 };
 
+// most states of a model whose filters are compiled at run time: kf_body's static LDS (UKF: 64 tiles of NX (3 NX + 2) doubles)
+// passes the 160 KB of a workgroup at NX = 10 (csrc/hilo_kf_kernel.h, refused in csrc/hilo_jit.hip::jit_kf_kernels)
+constexpr int KF_MAX_NX = 9;
+
 }  // namespace hilo

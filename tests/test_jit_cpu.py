@@ -124,3 +124,24 @@ def test_moving_horizon_estimator_policy_compiles_for_expression_models(name, co
 def test_moving_horizon_estimator_policy_compiles_for_a_zoo_functor_under_collocation():
     from hilo_mpc_amd import Model
     _compile(Model('chemostat4').user_source(), policy=3, coll_d=2, N=5)
+
+
+def _linear_chain(n):
+    """A cheap discrete linear model with n states (nothing to integrate, nothing transcendental)."""
+    from hilo_mpc_amd import Model
+    m = Model(name=f'chain{n}', discrete=True)
+    x = m.set_dynamical_states([f'x{i}' for i in range(n)])
+    m.set_dynamical_equations([0.9 * x[i] + 0.05 * x[(i + 1) % n] for i in range(n)])
+    m.set_measurement_equations([x[0]])
+    return m.setup(dt=1.)
+
+
+def test_filter_kernels_compile_up_to_nine_states_and_are_refused_beyond():
+    """All filter kernels of a model share one translation unit and `kf_body` stages 64 tiles of n_x (3 n_x + 2) doubles for the UKF in
+    static LDS: 133,632 bytes at n_x = 9, 164,352 > 163,840 at n_x = 10.  Nine states compile; ten (and seventeen - so the
+    particle statistics' own limit of 16 states is never reached by a model written as expressions) are refused by a host check
+    that names the limit, not by the compiler's log."""
+    _lib.check(_lib.lib().hilo_jit_precompile_kf(_linear_chain(9).user_source().encode()))
+    for n in (10, 17):
+        with pytest.raises(ValueError, match=f"built for up to 9 states.*160 KB of LDS at n_x = 10 - the model has {n}"):
+            _lib.check(_lib.lib().hilo_jit_precompile_kf(_linear_chain(n).user_source().encode()))

@@ -150,3 +150,94 @@ def test_batch_of_filters_tracks_the_state():
         s = pf.estimate(y=y)
         err.append(np.abs(np.abs(np.asarray(s['x'])) - np.abs(xt)))
     assert np.median(err[-1]) < 1.5 and np.all(np.isfinite(np.asarray(s['P'])))
+
+
+# ---- sizes at which the particle kernels take another path (csrc/hilo_kf_kernel.h: pf_kernel, pf_resample_kernel, pf_stats_kernel) ----
+EDGE = {'toy1d': dict(x0=[1.5], u=[], p=[], spread=.1),
+        'bioreactor3': dict(x0=[299.9, .217, 20.], u=[.01], p=[.15, 303.15, .13, .00025, 15., .14], spread=1e-4)}
+
+
+def resampling_reference(q, uni):
+    """numpy's `choice`: searchsorted on the normalised cumulative sum - and the draws whose index numpy itself changes when the cdf
+    moves by one ulp either way (the only ones a correct implementation with another summation order may place differently)."""
+    cdf = q.cumsum()
+    cdf /= cdf[-1]
+    ref = cdf.searchsorted(uni, side='right')
+    frail = (np.nextafter(cdf, np.inf).searchsorted(uni, side='right') != ref) | (np.nextafter(cdf, -np.inf).searchsorted(uni, side='right') != ref)
+    return ref, frail
+
+
+def test_resampling_reference_has_few_frail_draws():
+    """The seed of the edge test keeps numpy alone inside the cap of 0.5 % exempt draws (needs no device: uniform weights of the
+    same sizes stand in for the likelihoods)."""
+    for N in (2, 255, 257, 8192):
+        rng = np.random.default_rng(17 + N)
+        q = rng.uniform(.5, 1.5, N)
+        _, frail = resampling_reference(q / q.sum(), rng.random(N))
+        assert frail.mean() <= .005
+
+
+@pytest.mark.parametrize('N', [2, 255, 257, 8192])
+@pytest.mark.parametrize('name', ['toy1d', 'bioreactor3'])
+def test_particle_count_edges_vs_numpy(name, N):
+    """n_samples = 2 (fewer particles than the 256 threads; covariance over n - 1 = 1), 255 and 257 (chunks of one / a ragged last
+    chunk of the cumulative sum in `pf_resample_kernel`), 8192 (the limit: 67.5 KB of dynamic LDS, the `hipFuncSetAttribute` path)."""
+    import torch
+    from hilo_mpc_amd import _lib
+    from hilo_mpc_amd._device import ptr, stream_ptr, to_dev
+    e = EDGE[name]
+    m = Model(name)
+    m = m.setup(dt=1.) if name == 'toy1d' else m.discretize('rk4').setup(dt=.1)
+    om = omodels.get(name)
+    om = om if om.discrete else om.discretize(4)
+    x0, u, p = np.asarray(e['x0']), e['u'], e['p']
+    nx, ny, B = m.n_x, m.n_y, 2
+    pf = PF(m)
+    pf.setup(n_samples=N)
+    rng = np.random.default_rng(17 + N)
+    X = x0 * (1 + e['spread'] * rng.standard_normal((B, N, nx)))
+    w = .1 * e['spread'] * np.abs(x0) * rng.standard_normal((B, N, nx))
+    xn = om.f(x0[None], np.asarray(u)[None], np.asarray(p)[None], m.dt)
+    yref = om.h(xn, np.asarray(u)[None], np.asarray(p)[None], m.dt)[0]
+    # measurement noise as wide as the particle cloud (standard deviation ~ 2 spread |y|): the likelihood's argument z stays O(1) and
+    # its error eps |y| / sigma = eps / (2 spread) stays far below the 1e-9 asked of q (a tight R puts every particle in the tail,
+    # where exp(-z^2 / 2) multiplies that error by z^2)
+    R = np.diag(rng.uniform(.5, 2., ny) * (2 * e['spread'] * np.abs(yref)) ** 2)
+    v = rng.standard_normal((B, N, ny)) @ np.sqrt(R)
+    y = yref * (1 + e['spread'] * rng.standard_normal((B, ny)))
+    up = np.concatenate([u, p])[None] if (len(u) + len(p)) else None
+    Xp, Y, q = pf.function(X, y, up, w, v, R=R)
+    for b in range(B):
+        Xr, Yr, qr = opf.pf_function(om, m.dt, X[b], y[b], u, p, w[b], v[b], R)
+        np.testing.assert_allclose(Xp[b].cpu().numpy(), Xr, rtol=1e-11, atol=1e-13)
+        np.testing.assert_allclose(Y[b].cpu().numpy(), Yr, rtol=1e-11, atol=1e-13)
+        assert np.all(np.isfinite(qr)) and qr.max() > 0
+        np.testing.assert_allclose(q[b].cpu().numpy(), qr, rtol=1e-9, atol=1e-300)
+        assert abs(q[b].sum().item() - 1.) < 1e-12
+    uni = rng.random((B, N))
+    Xs, Ys = torch.empty_like(Xp), torch.empty_like(Y)
+    ind = torch.empty(B, N, dtype=torch.int32, device=Xp.device)
+    _lib.check(_lib.lib().hilo_pf_resample(pf._handle, B, N, ptr(Xp), ptr(Y), ptr(q), ptr(to_dev(uni, Xp.device)), ptr(Xs), ptr(Ys),
+                                           ptr(ind), stream_ptr(Xp.device)))
+    for b in range(B):
+        ref, frail = resampling_reference(q[b].cpu().numpy(), uni[b])
+        got = ind[b].cpu().numpy()
+        assert frail.mean() <= .005
+        np.testing.assert_array_equal(got[~frail], ref[~frail])
+        assert np.all(np.abs(got[frail] - ref[frail]) <= 1)
+        np.testing.assert_array_equal(Xs[b].cpu().numpy(), Xp[b].cpu().numpy()[got])
+        np.testing.assert_array_equal(Ys[b].cpu().numpy(), Y[b].cpu().numpy()[got])
+    add = 1e-3 * e['spread'] * np.abs(x0) * rng.standard_normal((B, N, nx))
+    Xa = Xs.clone()
+    xm, ym, P, lo, hi = pf._stats(Xa, Ys, to_dev(add, Xp.device))
+    Xh = Xs.cpu().numpy() + add
+    np.testing.assert_allclose(Xa.cpu().numpy(), Xh, rtol=0, atol=1e-15 * np.abs(x0).max())
+    for b in range(B):
+        np.testing.assert_allclose(xm[b].cpu().numpy(), Xh[b].mean(axis=0), rtol=1e-12)
+        np.testing.assert_allclose(ym[b].cpu().numpy(), Ys[b].cpu().numpy().mean(axis=0), rtol=1e-12)
+        # a deviation x - mean carries eps |x| of rounding, an entry of the covariance eps (|x_i| s_j + |x_j| s_i) with s = spread |x|
+        cov = np.atleast_2d(np.cov(Xh[b].T))
+        cov_atol = 16 * np.finfo(float).eps * e['spread'] * np.outer(np.abs(x0), np.abs(x0))
+        assert np.all(np.abs(P[b].cpu().numpy() - cov) <= 1e-9 * np.abs(cov) + cov_atol)
+        np.testing.assert_array_equal(lo[b].cpu().numpy(), Xh[b].min(axis=0))
+        np.testing.assert_array_equal(hi[b].cpu().numpy(), Xh[b].max(axis=0))
