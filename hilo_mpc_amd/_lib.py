@@ -29,7 +29,8 @@ class KfDesc(C.Structure):
 
 
 class SimOpts(C.Structure):
-    """hilo_sim_opts: method 0 = the handle's own map, 1 = HILO_SIM_DOPRI5, 2 = HILO_SIM_BDF."""
+    """hilo_sim_opts: method 0 = the handle's own map, 1 = HILO_SIM_DOPRI5, 2 = HILO_SIM_BDF, 3 = HILO_SIM_IDAS
+    (hilo_model_rollout_dae alone)."""
     _fields_ = [('method', C.c_int32), ('max_steps', C.c_int32), ('rtol', C.c_double), ('atol', C.c_double), ('h0', C.c_double),
                 ('t0', C.c_double)]
 
@@ -106,6 +107,7 @@ def _declare(lib):
         'hilo_pf_function': (C.c_int, [vp, i64, i32, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, vp]),
         'hilo_model_rollout': (C.c_int, [vp, P(SimOpts), i64, i32, vp, vp, i64, i64, vp, vp, vp, vp]),
         'hilo_model_rollout_resume': (C.c_int, [vp, P(SimOpts), i64, i32, vp, vp, i64, i64, vp, vp, vp, vp, vp]),
+        'hilo_model_rollout_dae': (C.c_int, [vp, P(SimOpts), i64, i32, vp, vp, vp, i64, i64, vp, vp, vp, vp, vp]),
         'hilo_model_linearize': (C.c_int, [vp, i64, vp, vp, i64, vp, vp, vp, vp]),
         'hilo_lqr_gain': (C.c_int, [i32, i32, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, P(LqrOpts), vp, vp, vp, vp]),
         'hilo_lqr_call': (C.c_int, [vp, P(LqrOpts), i64, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]),

@@ -6,8 +6,10 @@ controller's model], cp=p)`, `plant.simulate(u=u, p=p)`, `observer.estimate()` -
 observer runs alongside.  Here the plant is advanced on the device: with the controller's shooting map when it is the
 controller's own model (`NMPC.plant_step`), with `Model.step` for a plant model of its own (a continuous plant is integrated with
 eight classic Runge-Kutta steps per interval, or - set up with `Model.setup(solver='dopri5')` - under error control like the
-reference's CVODES), or by a callable `(x, u, p) -> x+`.  A time-variant plant (`Model.is_time_variant`) is advanced with
-`plant.simulate`, like the reference's, so that it keeps its clock: `run` starts it from x0 at the time of the plant's stored
+reference's CVODES; a plant with algebraic states set up with `solver='idas'` like its IDAS: the loop keeps the plant's algebraic
+states and starts the Newton iteration for the consistent start of each interval at those of the previous instant - the first
+interval of a `run` at the model's guess - so that z stays on its branch where g has several roots), or by a callable
+`(x, u, p) -> x+`.  A time-variant plant (`Model.is_time_variant`) is advanced with `plant.simulate`, like the reference's, so that it keeps its clock: `run` starts it from x0 at the time of the plant's stored
 solution (`plant.set_initial_conditions(x0, t0=...)` beforehand chooses it; 0 otherwise).  A controller without `optimize` but with `call` (the LQR) is asked
 `u = controller.call(x=x, p=p)` (control_loop.py:377)."""
 import numpy as np
@@ -35,6 +37,9 @@ class SimpleControlLoop:
                 self._plant_fun, self._plant = (lambda x, u, p: plant.step(x, u, p)[0]), plant
                 if getattr(plant, 'is_time_variant', lambda: False)():
                     self._plant_fun = self._simulate_plant
+                elif getattr(plant, '_solver', None) == 'idas':
+                    self._plant_fun = self._idas_plant
+        self._plant_z = None
         self.solution = None
 
     def _simulate_plant(self, x, u, p):
@@ -43,6 +48,12 @@ class SimpleControlLoop:
         plant.simulate(u=u, p=p, steps=1)
         xn = plant._sim['x'][-1]
         return torch.as_tensor(xn, device=x.device) if isinstance(x, torch.Tensor) else xn
+
+    def _idas_plant(self, x, u, p):
+        """One sampling interval of a plant with algebraic states; its z at the end is where the next interval's Newton iteration starts."""
+        xs, _, zs = self._plant.rollout(x, u, p, steps=1, z0=self._plant_z, return_z=True)
+        self._plant_z = zs[1]
+        return xs[1]
 
     def _measure(self, x):
         obs = self._observer
@@ -60,6 +71,7 @@ class SimpleControlLoop:
         tensor = isinstance(x0, torch.Tensor)
         x = x0 if tensor else np.atleast_2d(np.asarray(x0, dtype=float))
         X, U, S, E = [x], [], [], []
+        self._plant_z = None                               # an 'idas' plant starts this run at the model's guess
         if self._plant_fun == self._simulate_plant:        # the plant starts from x0 and goes on with its own clock
             sim = getattr(self._plant, '_sim', None)
             self._plant.set_initial_conditions(x, t0=sim['t'][-1] if sim else 0.)

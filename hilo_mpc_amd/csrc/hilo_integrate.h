@@ -36,7 +36,7 @@ namespace hilo {
 
 constexpr int SIM_MAP = 0;      // hilo_sim_opts.method: the handle's own map (model_step)
 constexpr int SIM_DOPRI5 = 1;   // HILO_SIM_DOPRI5
-constexpr int SIM_OK = 0, SIM_MAX_STEPS = 1, SIM_STEP_TOO_SMALL = 2;   // HILO_SIM_STATUS_*
+constexpr int SIM_OK = 0, SIM_MAX_STEPS = 1, SIM_STEP_TOO_SMALL = 2, SIM_IC_FAILED = 3;   // HILO_SIM_STATUS_* (3: SIM_IDAS alone)
 // Widest model the pair is built for: six slopes, the state and the trial point are alive at once (8 NX doubles = 16 NX
 // registers) next to the model's own temporaries.  Measured with a dense synthetic right-hand side (a sine, an exponential and
 // two products per state): 8 states 328 registers, 12 states 434, 16 states 507 of a lane's 512 - no scratch yet, no margin
@@ -344,10 +344,17 @@ HD void bdf_jacobian(const MEM& mem, const double* x, const double* u, const dou
 // stay rolled: every operand is in the store under a run-time row anyway, and unrolled the compiler keeps the whole matrix in
 // registers across the elimination (at 8 states 80 registers more, at 10 the difference between none and 132 bytes of scratch).
 template <int NX, class MEM>
+HD bool bdf_lu(const MEM& mem);
+template <int NX, class MEM>
 HD bool bdf_factor(const MEM& mem, double c) {
 #pragma unroll 1
   for (int i = 0; i < NX; ++i)
     for (int j = 0; j < NX; ++j) mem.LU(i, j) = (i == j ? 1.0 : 0.0) - c * mem.J(i, j);
+  return bdf_lu<NX>(mem);
+}
+// the elimination of bdf_factor on the matrix that stands in LU (shared with idas_factor below)
+template <int NX, class MEM>
+HD bool bdf_lu(const MEM& mem) {
 #pragma unroll 1
   for (int k = 0; k < NX; ++k) {
     int piv = k;
@@ -638,6 +645,438 @@ HD int bdf_interval(BdfCarry<M::NX>& c, const MEM& mem, double* x, const double*
   return c.status;
 }
 
+// ---- variable-order implicit integration of a model with algebraic states ---------------------------------------------------
+// `idas_interval` is `bdf_interval` on the semi-explicit index-1 DAE  dx/dt = f(x, z, u, p),  0 = g(x, z, u, p)  IN THE COMBINED
+// VECTOR w = [x; z] (N = NX + NZ entries), where the reference integrates such a model with IDAS: the NDF constants, the difference
+// table, change_D, the retry logic, the order selection and the dense output are the statements above with N in place of NX, on
+// the same store (BdfMem<N>, bdf_entries(N) doubles per instance).  With the mass matrix M = diag(I_NX, 0) and c = h / alpha[order]
+// the corrector solves M (psi + d) = c F(w_predict + d), F = [f; g]; the algebraic rows are divided by c.  What differs:
+//   Newton system   rows (I - c f_x, -c f_z) with residual c f - psi_x - d_x, rows (g_x, g_z) with residual -g: a small step leaves
+//                no rows of size c for the pivot search (idas_factor; the elimination and bdf_solve are shared)
+//   Jacobian     M::ode_z and M::alg on Dual<CH> seeded over the N columns of [x; z], ceil(N / 4) evaluations; neither dae_solve nor
+//                alg_jz.  A right-hand side is one ode_z and one alg in doubles; n_rhs counts such pairs
+//   tests        predictor, error test and Newton convergence test over all N components, scale = atol + rtol |w| (IDAS's default,
+//                suppress_algebraic off)
+//   consistent start   at the first step and at every restart z solves g(x, z, u, p) = 0 by Newton's method from the value it is
+//                handed (idas_newton_z: at most IDAS_IC_MAXITER sweeps, the exit test of dae_solve), then x' = f and
+//                z' = -g_z^-1 g_x f, so that D[1] = h w' holds for both parts; no convergence, a singular g_z or a non-finite
+//                value end the instance with SIM_IC_FAILED.  The first step is select_initial_step on the differential states
+//                through the reduced right-hand side: the trial point x + h0 f0 gets a Newton solve of its own for z
+//   sampling instants   x and z are read off the interpolant; z is then corrected by Newton sweeps on g(x, z) = 0 from the
+//                interpolated value until the residual is at round-off: what the caller receives is a consistent pair (the
+//                integrator's own state is not touched by that)
+// The sweeps of idas_newton_z evaluate `alg` on dual numbers seeded over z (value and g_z at once); they are not counted in n_rhs.
+constexpr int SIM_IDAS = 3;   // HILO_SIM_IDAS
+constexpr int IDAS_IC_MAXITER = 40;
+
+// J r' = r for a matrix of NZ x NZ entries held in registers, by Gaussian elimination with partial pivoting under static indices
+// (conditional swaps, as in dae_solve); false for a vanishing or non-finite pivot
+template <int NZ>
+HD bool idas_dense_solve(double* J, double* r) {
+  bool ok = true;
+#pragma unroll
+  for (int c = 0; c < NZ; ++c) {
+#pragma unroll
+    for (int q = c + 1; q < NZ; ++q) {
+      if (::fabs(J[q * NZ + c]) > ::fabs(J[c * NZ + c])) {
+#pragma unroll
+        for (int j = c; j < NZ; ++j) { const double t = J[c * NZ + j]; J[c * NZ + j] = J[q * NZ + j]; J[q * NZ + j] = t; }
+        const double t = r[c]; r[c] = r[q]; r[q] = t;
+      }
+    }
+    const double piv = ::fabs(J[c * NZ + c]);
+    ok = ok && piv > 0.0 && piv < INFINITY;
+    const double ip = 1.0 / J[c * NZ + c];
+#pragma unroll
+    for (int q = c + 1; q < NZ; ++q) {
+      const double f = J[q * NZ + c] * ip;
+#pragma unroll
+      for (int j = c + 1; j < NZ; ++j) J[q * NZ + j] -= f * J[c * NZ + j];
+      r[q] -= f * r[c];
+    }
+  }
+#pragma unroll
+  for (int c = NZ - 1; c >= 0; --c) {
+    double acc = r[c];
+#pragma unroll
+    for (int j = c + 1; j < NZ; ++j) acc -= J[c * NZ + j] * r[j];
+    r[c] = acc / J[c * NZ + c];
+  }
+  return ok;
+}
+
+// Newton's method on g(x, z, u, p) = 0 for z, in place, from the z it is handed: value and dg/dz of a sweep from `alg` on dual
+// numbers seeded over z.  Ends like dae_solve - after the second sweep that found the residual at round-off, 1e-13 (1 + |z|) - and
+// answers false when IDAS_IC_MAXITER sweeps did not get there, for a singular dg/dz and for a non-finite value.
+template <class M>
+HD bool idas_newton_z(const double* x, double* z, const double* u, const double* p) {
+  constexpr int NX = M::NX, NZ = M::NZ, NU = M::NU, CH = NZ < 4 ? NZ : 4;
+  int done = 0;
+  bool ok = true;
+#pragma unroll 1
+  for (int it = 0; it < IDAS_IC_MAXITER; ++it) {
+    // No lane leaves the loop on its own: on the device the exit is a vote of the wave, and a lane that is done -
+    // converged or failed - no longer changes its z, so its result does not depend on how long its neighbours go on.
+    const bool active = ok && done < 2;
+#if defined(__HIP_DEVICE_COMPILE__)
+    if (!__any((int)active)) break;
+#else
+    if (!active) break;
+#endif
+    double r[NZ], J[NZ * NZ];
+#pragma unroll
+    for (int c0 = 0; c0 < NZ; c0 += CH) {
+      Dual<CH> xd[NX], zd[NZ], ud[NU > 0 ? NU : 1], gd[NZ];
+#pragma unroll
+      for (int i = 0; i < NX; ++i) xd[i] = Dual<CH>(x[i]);
+#pragma unroll
+      for (int i = 0; i < NU; ++i) ud[i] = Dual<CH>(u[i]);
+#pragma unroll
+      for (int i = 0; i < NZ; ++i) {
+        zd[i] = Dual<CH>(z[i]);
+        if (i >= c0 && i < c0 + CH) zd[i].d[i - c0] = 1.0;
+      }
+      M::alg(xd, zd, ud, p, gd);
+#pragma unroll
+      for (int i = 0; i < NZ; ++i) {
+        r[i] = gd[i].v;
+#pragma unroll
+        for (int q = 0; q < CH; ++q)
+          if (c0 + q < NZ) J[i * NZ + c0 + q] = gd[i].d[q];
+      }
+    }
+    double rmax = 0.0, zmax = 0.0;
+    bool good = true;
+#pragma unroll
+    for (int i = 0; i < NZ; ++i) {
+      rmax = ::fmax(rmax, ::fabs(r[i]));
+      zmax = ::fmax(zmax, ::fabs(z[i]));
+      good = good && ::fabs(r[i]) < INFINITY;
+    }
+    good = idas_dense_solve<NZ>(J, r) && good;
+#pragma unroll
+    for (int i = 0; i < NZ; ++i) good = good && ::fabs(z[i] - r[i]) < INFINITY;
+#pragma unroll
+    for (int i = 0; i < NZ; ++i) z[i] = active && good ? z[i] - r[i] : z[i];
+    ok = active ? good : ok;
+    done += (int)(active && good && rmax <= 1e-13 * (1.0 + zmax));   // the values had converged before this sweep
+  }
+  return ok && done >= 2;
+}
+
+// [f; g] at w = [x; z] in doubles: one right-hand side
+template <class M>
+HD void idas_rhs(const double* w, const double* u, const double* p, double* F) {
+  M::ode_z(w, w + M::NX, u, p, F);
+  M::alg(w, w + M::NX, u, p, F + M::NX);
+}
+
+// d[f; g] / d[x; z] at w into the store, CH columns per evaluation of M::ode_z and M::alg on Dual<CH>
+template <class M, class MEM>
+HD void idas_jacobian(const MEM& mem, const double* w, const double* u, const double* p) {
+  constexpr int NX = M::NX, NZ = M::NZ, NU = M::NU, N = NX + NZ, CH = N < 4 ? N : 4;
+#pragma unroll
+  for (int c0 = 0; c0 < N; c0 += CH) {
+    Dual<CH> wd[N], ud[NU > 0 ? NU : 1], Fd[N];
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+      wd[i] = Dual<CH>(w[i]);
+      if (i >= c0 && i < c0 + CH) wd[i].d[i - c0] = 1.0;
+    }
+#pragma unroll
+    for (int i = 0; i < NU; ++i) ud[i] = Dual<CH>(u[i]);
+    M::ode_z(wd, wd + NX, ud, p, Fd);
+    M::alg(wd, wd + NX, ud, p, Fd + NX);
+#pragma unroll
+    for (int i = 0; i < N; ++i)
+#pragma unroll
+      for (int q = 0; q < CH; ++q)
+        if (c0 + q < N) mem.J(i, c0 + q) = Fd[i].d[q];
+  }
+}
+
+// factors of [I - c f_x, -c f_z; g_x, g_z] (the sibling of bdf_factor: the algebraic rows are not scaled by c)
+template <int NX, int NZ, class MEM>
+HD bool idas_factor(const MEM& mem, double c) {
+  constexpr int N = NX + NZ;
+#pragma unroll 1
+  for (int i = 0; i < N; ++i)
+    for (int j = 0; j < N; ++j) mem.LU(i, j) = i < NX ? (i == j ? 1.0 : 0.0) - c * mem.J(i, j) : mem.J(i, j);
+  return bdf_lu<N>(mem);
+}
+
+// The consistent start of an integration from (x, z-guess) in w: z <- the root of g, the Jacobian at the consistent point, w', the
+// first step and the difference table.  Called by idas_interval on the first call after bdf_init / bdf_restart; the roll-out calls
+// it itself at row 0, whose z it records.  Returns c.status (SIM_OK or SIM_IC_FAILED).
+template <class M, class MEM>
+HD int idas_start(BdfCarry<M::NX + M::NZ>& c, const MEM& mem, double* w, const double* u, const double* p, double rtol, double atol,
+                  double h0) {
+  constexpr int NX = M::NX, NZ = M::NZ, N = NX + NZ;
+  if (c.status != SIM_OK || c.started) return c.status;
+  if (!idas_newton_z<M>(w, w + NX, u, p)) return c.status = SIM_IC_FAILED;
+  double wp[N];   // [x'; z']
+  idas_rhs<M>(w, u, p, wp);
+  ++c.n_rhs;
+  idas_jacobian<M>(mem, w, u, p);
+  ++c.n_jac;
+  {
+    double Jz[NZ * NZ];
+#pragma unroll
+    for (int a = 0; a < NZ; ++a) {
+      double s = 0.0;
+#pragma unroll
+      for (int j = 0; j < NX; ++j) s += mem.J(NX + a, j) * wp[j];
+      wp[NX + a] = -s;
+#pragma unroll
+      for (int q = 0; q < NZ; ++q) Jz[a * NZ + q] = mem.J(NX + a, NX + q);
+    }
+    bool ok = idas_dense_solve<NZ>(Jz, wp + NX);
+#pragma unroll
+    for (int i = 0; i < N; ++i) ok = ok && ::fabs(wp[i]) < INFINITY;
+    if (!ok) return c.status = SIM_IC_FAILED;
+  }
+  if (h0 > 0.0) {
+    c.h = ::fmin(h0, c.t_bound);
+  } else {   // select_initial_step with order = 1 on dx/dt = f(x, zeta(x))
+    double scale[NX], w1[N], f1[N];
+#pragma unroll
+    for (int i = 0; i < NX; ++i) scale[i] = atol + ::fabs(w[i]) * rtol;
+    const double d0 = dopri5_rms<NX>(w, scale), d1 = dopri5_rms<NX>(wp, scale);
+    double hh = (d0 < 1e-5 || d1 < 1e-5) ? 1e-6 : 0.01 * d0 / d1;
+    hh = ::fmin(hh, c.t_bound);
+#pragma unroll
+    for (int i = 0; i < N; ++i) w1[i] = i < NX ? w[i] + hh * wp[i] : w[i];
+    if (idas_newton_z<M>(w1, w1 + NX, u, p)) {
+      idas_rhs<M>(w1, u, p, f1);
+      ++c.n_rhs;
+#pragma unroll
+      for (int i = 0; i < NX; ++i) f1[i] -= wp[i];
+      const double d2 = dopri5_rms<NX>(f1, scale) / hh;
+      const double h1 = (d1 <= 1e-15 && d2 <= 1e-15) ? ::fmax(1e-6, hh * 1e-3) : ::pow(0.01 / ::fmax(d1, d2), 0.5);
+      c.h = ::fmin(::fmin(100.0 * hh, h1), c.t_bound);
+    } else {
+      c.h = hh;   // the algebraic equations have no root at the trial point: the first guess stands
+    }
+    if (!(c.h > 0.0)) c.h = c.t_bound;   // a non-finite estimate: the Newton iteration of the step fails and finds the step (or gives up)
+  }
+  for (int r = 0; r < BDF_MAX_ORDER + 3; ++r)
+#pragma unroll
+    for (int i = 0; i < N; ++i) mem.D(r, i) = r == 0 ? w[i] : (r == 1 ? wp[i] * c.h : 0.0);
+  c.t = 0.0;
+  c.order = 1;
+  c.n_equal = 0;
+  c.have_lu = false;
+  c.started = true;
+  return c.status;
+}
+
+// bdf_change_D as ONE function of the kernel instead of five inlined copies (the five copies' registers are what pushed the widest
+// models' kernels into live-range splits at the loop exits).  Not `HD`: that macro forces inlining.
+template <int N, class MEM>
+__host__ __device__ __attribute__((noinline)) void idas_change_D(MEM mem, int order, double factor) {
+  bdf_change_D<N>(mem, order, factor);
+}
+
+// Advances the DAE until the integration time reaches t_target (<= c.t_bound) and reads w = [x; z] at t_target off the interpolant,
+// z corrected onto g(x, z) = 0.  On the first call after bdf_init / bdf_restart w holds the initial x and the start of the Newton
+// iteration for z.  Returns c.status; on a failure w is left as it was (the caller discards it).  The correction of z at t_target is
+// held to the exit test of the consistent start: where its sweeps do not bring the residual to round-off - a badly scaled g, a
+// singular dg/dz on the way - the instance ends with SIM_IC_FAILED at THAT instant, whichever it is.  The other arguments:
+// bdf_interval's.
+template <class M, class MEM>
+HD int idas_interval(BdfCarry<M::NX + M::NZ>& c, const MEM& mem, double* w, const double* u, const double* p, double t_target,
+                     double rtol, double atol, double h0, int max_steps) {
+  constexpr int NX = M::NX, NZ = M::NZ, N = NX + NZ;
+  constexpr double EPS = 2.220446049250313e-16;
+  if (c.status != SIM_OK) return c.status;
+  if (!c.started && idas_start<M>(c, mem, w, u, p, rtol, atol, h0) != SIM_OK) return c.status;
+  const double newton_tol = ::fmax(10.0 * EPS / rtol, ::fmin(0.03, ::sqrt(rtol)));
+  int attempts = 0;
+  while (c.t < t_target) {   // one pass: scipy's _step_impl
+    const double min_step = 10.0 * (::nextafter(c.t, INFINITY) - c.t);
+    double h = c.h;
+    int order = c.order;
+    if (h < min_step) {
+      idas_change_D<N>(mem, order, min_step / h);
+      h = min_step;
+      c.n_equal = 0;
+    }
+    bool current_jac = false, accepted = false;
+    double t_new = c.t, safety = 0.0, error_norm = 0.0;
+    double scale[N], d[N];
+    while (!accepted) {
+      if (attempts >= max_steps) return c.status = SIM_MAX_STEPS;
+      if (!(h >= min_step)) return c.status = SIM_STEP_TOO_SMALL;
+      ++attempts;
+      t_new = c.t + h;
+      if (t_new > c.t_bound) {
+        t_new = c.t_bound;
+        idas_change_D<N>(mem, order, (t_new - c.t) / h);
+        c.n_equal = 0;
+        c.have_lu = false;
+      }
+      h = t_new - c.t;
+      double y_predict[N], psi[N], y[N];
+#pragma unroll
+      for (int i = 0; i < N; ++i) {
+        y_predict[i] = mem.D(0, i);
+        psi[i] = 0.0;
+      }
+      for (int j = 1; j <= order; ++j) {
+        const double g = bdf_gamma(j);
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+          const double v = mem.D(j, i);
+          y_predict[i] += v;
+          psi[i] += v * g;
+        }
+      }
+      const double alpha = bdf_alpha(order);
+#pragma unroll
+      for (int i = 0; i < N; ++i) {
+        scale[i] = atol + rtol * ::fabs(y_predict[i]);
+        psi[i] /= alpha;
+      }
+      const double cc = h / alpha;
+      bool converged = false;
+      int n_iter = 0;
+      while (!converged) {
+        if (!c.have_lu) {
+          c.have_lu = idas_factor<NX, NZ>(mem, cc);
+          ++c.n_lu;
+        }
+        if (c.have_lu) {   // solve_bdf_system
+          double dy_norm_old = -1.0;   // (none yet)
+#pragma unroll
+          for (int i = 0; i < N; ++i) {
+            d[i] = 0.0;
+            y[i] = y_predict[i];
+          }
+#pragma unroll 1
+          for (int k = 0; k < BDF_NEWTON_MAXITER; ++k) {
+            n_iter = k + 1;
+            double f[N];
+            idas_rhs<M>(y, u, p, f);
+            ++c.n_rhs;
+            bool finite = true;
+#pragma unroll
+            for (int i = 0; i < N; ++i) finite = finite && ::fabs(f[i]) < INFINITY;
+            if (!finite) break;
+#pragma unroll
+            for (int i = 0; i < N; ++i) f[i] = i < NX ? cc * f[i] - psi[i] - d[i] : -f[i];
+            bdf_solve<N>(mem, f);   // f: dy
+            const double dy_norm = dopri5_rms<N>(f, scale);
+            if (!(dy_norm < INFINITY)) break;
+            const bool have_rate = dy_norm_old >= 0.0;
+            const double rate = dy_norm / dy_norm_old;
+            if (have_rate && !(rate < 1.0 && ::pow(rate, (double)(BDF_NEWTON_MAXITER - k)) / (1.0 - rate) * dy_norm <= newton_tol)) break;
+#pragma unroll
+            for (int i = 0; i < N; ++i) {
+              y[i] += f[i];
+              d[i] += f[i];
+            }
+            if (dy_norm == 0.0 || (have_rate && rate / (1.0 - rate) * dy_norm < newton_tol)) {
+              converged = true;
+              break;
+            }
+            dy_norm_old = dy_norm;
+          }
+        }
+        if (!converged) {
+          if (current_jac) break;
+          idas_jacobian<M>(mem, y_predict, u, p);
+          ++c.n_jac;
+          c.have_lu = false;
+          current_jac = true;
+        }
+      }
+      if (!converged) {
+        h *= 0.5;
+        idas_change_D<N>(mem, order, 0.5);
+        c.n_equal = 0;
+        c.have_lu = false;
+        ++c.n_rej;
+        continue;
+      }
+      safety = 0.9 * (2 * BDF_NEWTON_MAXITER + 1) / (2 * BDF_NEWTON_MAXITER + n_iter);
+      const double ec = bdf_error_const(order);
+      double s = 0.0;
+#pragma unroll
+      for (int i = 0; i < N; ++i) {
+        scale[i] = atol + rtol * ::fabs(y[i]);
+        const double q = ec * d[i] / scale[i];
+        s += q * q;
+      }
+      error_norm = ::sqrt(s / N);
+      if (!(error_norm <= 1.0)) {   // (a non-finite estimate fails the comparison: a rejection)
+        const double factor = ::fmax(BDF_MIN_FACTOR, safety * ::pow(error_norm, -1.0 / (order + 1)));
+        h *= factor;
+        idas_change_D<N>(mem, order, factor);
+        c.n_equal = 0;   // the factors stay: the iteration had no trouble converging
+        ++c.n_rej;
+      } else {
+        accepted = true;
+      }
+    }
+    ++c.n_equal;
+    ++c.n_acc;
+    c.t = t_new;
+    c.h = h;
+    // D^{j+1} y_n = D^j y_n - D^j y_{n-1}, d = D^{order+1} y_n
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+      mem.D(order + 2, i) = d[i] - mem.D(order + 1, i);
+      mem.D(order + 1, i) = d[i];
+    }
+    for (int j = order; j >= 0; --j)
+#pragma unroll
+      for (int i = 0; i < N; ++i) mem.D(j, i) += mem.D(j + 1, i);
+    if (c.n_equal < order + 1) continue;
+    double sm = 0.0, sp = 0.0;
+    {
+      const double em = bdf_error_const(order - 1), ep = bdf_error_const(order + 1);
+#pragma unroll
+      for (int i = 0; i < N; ++i) {
+        const double qm = em * mem.D(order, i) / scale[i], qp = ep * mem.D(order + 2, i) / scale[i];
+        sm += qm * qm;
+        sp += qp * qp;
+      }
+    }
+    const double error_m_norm = order > 1 ? ::sqrt(sm / N) : INFINITY;
+    const double error_p_norm = order < BDF_MAX_ORDER ? ::sqrt(sp / N) : INFINITY;
+    const double fm = ::pow(error_m_norm, -1.0 / order), f0 = ::pow(error_norm, -1.0 / (order + 1)),
+                 fp = ::pow(error_p_norm, -1.0 / (order + 2));
+    double fmax_ = fm;   // argmax: the first of equal ones
+    int delta = -1;
+    if (f0 > fmax_) { fmax_ = f0; delta = 0; }
+    if (fp > fmax_) { fmax_ = fp; delta = 1; }
+    if (order + delta < 1) delta = 0;   // (order 1: fm is 0 and can only win against two zeros)
+    order += delta;
+    c.order = order;
+    const double factor = ::fmin(BDF_MAX_FACTOR, safety * fmax_);
+    c.h *= factor;
+    idas_change_D<N>(mem, order, factor);
+    c.n_equal = 0;
+    c.have_lu = false;
+  }
+  // BdfDenseOutput at t_target, then z onto g(x, z) = 0
+  double acc[N];
+#pragma unroll
+  for (int i = 0; i < N; ++i) acc[i] = 0.0;
+  double prod = 1.0;
+  for (int j = 0; j < c.order; ++j) {
+    prod *= (t_target - (c.t - c.h * j)) / (c.h * (1 + j));
+#pragma unroll
+    for (int i = 0; i < N; ++i) acc[i] += mem.D(j + 1, i) * prod;
+  }
+#pragma unroll
+  for (int i = 0; i < N; ++i) acc[i] += mem.D(0, i);
+  if (!idas_newton_z<M>(acc, acc + NX, u, p)) return c.status = SIM_IC_FAILED;
+#pragma unroll
+  for (int i = 0; i < N; ++i) w[i] = acc[i];
+  return c.status;
+}
+
 constexpr int ROLLOUT_TPB = 64;   // one wave per workgroup: a slow instance holds back 63 others, not 255
 
 // One instance per lane.  X [steps + 1][batch][NX] (row 0: x0), Y [steps][batch][NY] or null, stats [batch][4] (status, accepted,
@@ -785,6 +1224,79 @@ __device__ __forceinline__ void rollout_bdf_body(const KP& kp, const SimParams& 
       if (Y != nullptr) {
         double yy[NY];
         model_meas_at<M>(t0 + (k + 1) * kp.dt, x, u, p, kp.dt, yy);
+        double* Yk = Y + ((int64_t)k * batch + b) * NY;
+#pragma unroll
+        for (int i = 0; i < NY; ++i) Yk[i] = ok ? yy[i] : nan;
+      }
+    }
+  }
+  if (stats != nullptr) {
+    stats[b * 4 + 0] = c.status;
+    stats[b * 4 + 1] = c.n_acc;
+    stats[b * 4 + 2] = c.n_rej;
+    stats[b * 4 + 3] = c.n_rhs;
+  }
+}
+
+// The SIM_IDAS path: rollout_bdf_body for a model with algebraic states (idas_interval in w = [x; z]).  z0 [batch][NZ] or null: the
+// start of the Newton iteration for the consistent initial z (null: M::z_guess); Z [steps + 1][batch][NZ] or null: the algebraic
+// states at the sampling instants, row 0 the consistent initial values.  Inputs held: one integration over the roll-out.  An input
+// sequence: a restart at every instant - a consistent start with the new inputs from the z of the previous instant (z jumps when g
+// names u), order 1, a fresh first step.  Y[k] = meas_z(x_{k+1}, z_{k+1}, u_k, p) on the pair written to X and Z: no further solve.
+// An instance that fails gets NaN in X, Z and Y from the first instant it did not reach; with SIM_IC_FAILED at the very start that is
+// row 1 of X and row 0 of Z.
+template <class M, class KP>
+__device__ __forceinline__ void rollout_idas_body(const KP& kp, const SimParams& sp, int64_t batch, int steps,
+                                                  const double* __restrict__ x0, const double* __restrict__ z0,
+                                                  const double* __restrict__ up, int64_t up_stride, int64_t up_step,
+                                                  double* __restrict__ X, double* __restrict__ Z, double* __restrict__ Y,
+                                                  int* __restrict__ stats, lds_double* lds) {
+  constexpr int NX = M::NX, NZ = M::NZ, N = NX + NZ, NU = M::NU, NP = M::NP, NY = M::NY;
+  static_assert(!M::DISCRETE && NZ > 0 && N <= BDF_MAX_NX, "SIM_IDAS integrates a continuous model with algebraic states, NX + NZ <= BDF_MAX_NX");
+  const int64_t b = (int64_t)blockIdx.x * ROLLOUT_TPB + threadIdx.x;
+  if (b >= batch) return;
+  double w[N], upv[NU + NP > 0 ? NU + NP : 1];
+#pragma unroll
+  for (int i = 0; i < NX; ++i) {
+    w[i] = x0[b * NX + i];
+    X[b * NX + i] = w[i];
+  }
+#pragma unroll
+  for (int i = 0; i < NZ; ++i) w[NX + i] = z0 != nullptr ? z0[b * NZ + i] : M::z_guess(i);
+  const BdfMem<N, ROLLOUT_TPB, lds_double*> mem = {lds + threadIdx.x};
+  BdfCarry<N> c;
+  const bool held = up_step == 0;
+  bdf_init(c, held ? steps * kp.dt : kp.dt);
+  const double nan = __builtin_nan("");
+  for (int k = 0; k < steps; ++k) {
+    if (k == 0 || !held) {
+      const double* src = up + (int64_t)k * up_step + b * up_stride;
+#pragma unroll
+      for (int i = 0; i < NU + NP; ++i) upv[i] = src[i];
+      if (k > 0) bdf_restart(c, kp.dt);
+    }
+    const double* u = upv;
+    const double* p = upv + NU;
+    if (k == 0) {
+      const bool ok0 = idas_start<M>(c, mem, w, u, p, sp.rtol, sp.atol, sp.h0) == SIM_OK;
+      if (Z != nullptr) {
+#pragma unroll
+        for (int i = 0; i < NZ; ++i) Z[b * NZ + i] = ok0 ? w[NX + i] : nan;
+      }
+    }
+    const bool ok = idas_interval<M>(c, mem, w, u, p, held ? (k + 1) * kp.dt : kp.dt, sp.rtol, sp.atol, sp.h0, sp.max_steps) == SIM_OK;
+    double* Xk = X + ((int64_t)(k + 1) * batch + b) * NX;
+#pragma unroll
+    for (int i = 0; i < NX; ++i) Xk[i] = ok ? w[i] : nan;
+    if (Z != nullptr) {
+      double* Zk = Z + ((int64_t)(k + 1) * batch + b) * NZ;
+#pragma unroll
+      for (int i = 0; i < NZ; ++i) Zk[i] = ok ? w[NX + i] : nan;
+    }
+    if constexpr (NY > 0) {
+      if (Y != nullptr) {
+        double yy[NY];
+        M::meas_z(w, w + NX, u, p, yy);
         double* Yk = Y + ((int64_t)k * batch + b) * NY;
 #pragma unroll
         for (int i = 0; i < NY; ++i) Yk[i] = ok ? yy[i] : nan;

@@ -61,6 +61,9 @@ struct JitKfKernels {
   int rollout_scratch = 0;                       // bytes of scratch per lane of that kernel (0: everything in registers)
   hipFunction_t rollout_bdf = nullptr;           // the same with the implicit method (hilo_integrate.h::rollout_bdf_body, SIM_BDF)
   int rollout_bdf_scratch = 0;                   // bytes of scratch per lane of that kernel
+  hipFunction_t rollout_idas = nullptr;          // a model with algebraic states in [x; z] (hilo_integrate.h::rollout_idas_body, SIM_IDAS);
+  int rollout_idas_scratch = 0;                  // an empty kernel for every other model.  Bytes of scratch per lane of that kernel
+  int nz = 0;                                    // algebraic states of the functor (hilo_models.h::model_nz)
   hipFunction_t lqr_call = nullptr, lqr_linearize = nullptr;   // regulator gains and Jacobians of the model's map (hilo_lqr.h)
   int lqr_scratch = 0;                           // bytes of scratch per lane of the two (the larger)
   int lqr_ok = 0;                                // the two are built for this model (hilo_lqr.h::LqrModelOk)

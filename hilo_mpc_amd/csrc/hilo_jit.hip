@@ -448,6 +448,18 @@ extern "C" __global__ __launch_bounds__(ROLLOUT_TPB) void hilo_user_rollout_bdf(
     rollout_body<UserModel, SIM_BDF>(kp, sp, batch, steps, x0, up, up_stride, up_step, X, Y, stats, (lds_double*)bdf_lds, t0);
   }
 }
+extern "C" __global__ __launch_bounds__(ROLLOUT_TPB) void hilo_user_rollout_idas(KfParams kp, SimParams sp, int64_t batch, int steps,
+                                                                                 const double* __restrict__ x0,
+                                                                                 const double* __restrict__ z0,
+                                                                                 const double* __restrict__ up, int64_t up_stride,
+                                                                                 int64_t up_step, double* __restrict__ X,
+                                                                                 double* __restrict__ Z, double* __restrict__ Y,
+                                                                                 int* __restrict__ stats) {
+  if constexpr (model_nz<UserModel>::value > 0 && UserModel::NX + model_nz<UserModel>::value <= BDF_MAX_NX && !UserModel::DISCRETE) {
+    __shared__ double idas_lds[bdf_entries(UserModel::NX + model_nz<UserModel>::value) * ROLLOUT_TPB];
+    rollout_idas_body<UserModel>(kp, sp, batch, steps, x0, z0, up, up_stride, up_step, X, Z, Y, stats, (lds_double*)idas_lds);
+  }
+}
 extern "C" __global__ __launch_bounds__(64) void hilo_user_lqr_call(KfParams kp, LqrParams o, int64_t batch, const double* __restrict__ x,
                                                                     const double* __restrict__ x_eq, const double* __restrict__ u_eq,
                                                                     const double* __restrict__ p, int64_t p_stride,
@@ -467,6 +479,7 @@ extern "C" __global__ void hilo_user_kf_info(int* o) {
   o[0] = UserModel::NX; o[1] = UserModel::NU; o[2] = UserModel::NP; o[3] = UserModel::NY; o[4] = UserModel::DISCRETE ? 1 : 0;
   o[5] = LqrModelOk<UserModel>::value ? 1 : 0;
   o[6] = model_time_variant<UserModel>::value ? 1 : 0;
+  o[7] = model_nz<UserModel>::value;
 }
 )";
   std::vector<std::string> opts;
@@ -501,6 +514,8 @@ extern "C" __global__ void hilo_user_kf_info(int* o) {
   if (hipFuncGetAttribute(&k.rollout_scratch, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, k.rollout) != hipSuccess) k.rollout_scratch = 0;
   HILO_HIP_CHECK(hipModuleGetFunction(&k.rollout_bdf, mod, "hilo_user_rollout_bdf"));
   if (hipFuncGetAttribute(&k.rollout_bdf_scratch, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, k.rollout_bdf) != hipSuccess) k.rollout_bdf_scratch = 0;
+  HILO_HIP_CHECK(hipModuleGetFunction(&k.rollout_idas, mod, "hilo_user_rollout_idas"));
+  if (hipFuncGetAttribute(&k.rollout_idas_scratch, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, k.rollout_idas) != hipSuccess) k.rollout_idas_scratch = 0;
   HILO_HIP_CHECK(hipModuleGetFunction(&k.lqr_call, mod, "hilo_user_lqr_call"));
   HILO_HIP_CHECK(hipModuleGetFunction(&k.lqr_linearize, mod, "hilo_user_lqr_linearize"));
   {
@@ -515,11 +530,12 @@ extern "C" __global__ void hilo_user_kf_info(int* o) {
   HILO_HIP_CHECK(hipMalloc((void**)&dinfo, sizeof(int) * 8));
   void* args[] = {&dinfo};
   HILO_HIP_CHECK(hipModuleLaunchKernel(info, 1, 1, 1, 1, 1, 1, 0, nullptr, args, nullptr));
-  int hinfo[7];
-  HILO_HIP_CHECK(hipMemcpy(hinfo, dinfo, sizeof(int) * 7, hipMemcpyDeviceToHost));
+  int hinfo[8];
+  HILO_HIP_CHECK(hipMemcpy(hinfo, dinfo, sizeof(int) * 8, hipMemcpyDeviceToHost));
   for (int i = 0; i < 5; ++i) k.dims[i] = hinfo[i];
   k.lqr_ok = hinfo[5];
   k.time_variant = hinfo[6];
+  k.nz = hinfo[7];
   HILO_HIP_CHECK(hipFree(dinfo));
   {
     hipDeviceptr_t gptr = nullptr;

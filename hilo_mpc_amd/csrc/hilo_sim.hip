@@ -52,7 +52,8 @@ static int rollout_launch(const KfParams& kp, const SimParams& sp, int64_t batch
 using namespace hilo;
 
 static_assert(HILO_SIM_DOPRI5_MAX_NX == DOPRI5_MAX_NX && HILO_SIM_DOPRI5 == SIM_DOPRI5 && HILO_SIM_STATUS_MAX_STEPS == SIM_MAX_STEPS &&
-              HILO_SIM_STATUS_STEP_TOO_SMALL == SIM_STEP_TOO_SMALL && HILO_SIM_BDF == SIM_BDF && HILO_SIM_BDF_MAX_NX == BDF_MAX_NX,
+              HILO_SIM_STATUS_STEP_TOO_SMALL == SIM_STEP_TOO_SMALL && HILO_SIM_BDF == SIM_BDF && HILO_SIM_BDF_MAX_NX == BDF_MAX_NX &&
+              HILO_SIM_IDAS == SIM_IDAS && HILO_SIM_STATUS_IC_FAILED == SIM_IC_FAILED,
               "include/hilo_hip.h and csrc/hilo_integrate.h disagree");
 
 // hilo_model_rollout (h NULL) and hilo_model_rollout_resume
@@ -136,6 +137,58 @@ extern "C" int hilo_model_rollout(hilo_kf* kf, const hilo_sim_opts* opts, int64_
                                   const double* up, int64_t up_stride, int64_t up_step, double* X, double* Y, int32_t* stats,
                                   void* stream) {
   return rollout_impl(kf, opts, batch, steps, x0, up, up_stride, up_step, X, Y, stats, nullptr, stream);
+}
+
+// A model with algebraic states under HILO_SIM_IDAS (csrc/hilo_integrate.h::rollout_idas_body).  The zoo has no such model: the
+// kernel lives in the run-time compiled unit alone.
+extern "C" int hilo_model_rollout_dae(hilo_kf* kf, const hilo_sim_opts* opts, int64_t batch, int steps, const double* x0,
+                                      const double* z0, const double* up, int64_t up_stride, int64_t up_step, double* X, double* Z,
+                                      double* Y, int32_t* stats, void* stream) {
+  HILO_REQUIRE(kf, "hilo_model_rollout_dae: NULL handle");
+  HILO_REQUIRE(batch >= 0 && steps >= 1, "hilo_model_rollout_dae: need batch >= 0 and steps >= 1");
+  SimParams sp = {SIM_MAP, 10000, 1e-6, 1e-8, 0.0};
+  if (opts) {
+    sp.method = opts->method;
+    if (opts->max_steps > 0) sp.max_steps = opts->max_steps;
+    if (opts->rtol > 0.0) sp.rtol = opts->rtol;
+    if (opts->atol > 0.0) sp.atol = opts->atol;
+    if (opts->h0 > 0.0) sp.h0 = opts->h0;
+    HILO_REQUIRE(opts->t0 == opts->t0 && ::fabs(opts->t0) < INFINITY, "hilo_model_rollout_dae: t0 must be finite");
+  }
+  if (sp.method != SIM_IDAS)
+    return fail(HILO_ENOTSUP, "hilo_model_rollout_dae: method %d; this entry integrates with HILO_SIM_IDAS alone (the other methods: "
+                              "hilo_model_rollout)", sp.method);
+  const int nz = kf->desc.model_id == 100 /* HILO_MODEL_USER */ ? kf->jit.nz : 0;
+  if (nz <= 0)
+    return fail(HILO_ENOTSUP, "hilo_model_rollout_dae: HILO_SIM_IDAS integrates a model with algebraic states; this handle's model has "
+                              "none (HILO_SIM_BDF through hilo_model_rollout integrates it)");
+  if (kf->discrete || !kf->kp.continuous)
+    return fail(HILO_ENOTSUP, "hilo_model_rollout_dae: HILO_SIM_IDAS integrates a continuous model; this handle holds a discrete "
+                              "(or discretised) one");
+  if (kf->nx + nz > HILO_SIM_BDF_MAX_NX)
+    return fail(HILO_ENOTSUP, "hilo_model_rollout_dae: HILO_SIM_IDAS keeps its difference table, the Jacobian and its factors in the LDS "
+                              "of one workgroup and is built for up to %d differential and algebraic states together; the model has "
+                              "%d + %d", HILO_SIM_BDF_MAX_NX, kf->nx, nz);
+  if (kf->jit.rollout_idas_scratch > 0)
+    return fail(HILO_ENOTSUP, "hilo_model_rollout_dae: the compiled equations of this model leave HILO_SIM_IDAS %d bytes of scratch "
+                              "memory per lane; the method is built to keep its vectors in registers", kf->jit.rollout_idas_scratch);
+  if (batch == 0) return HILO_OK;
+  HILO_REQUIRE(x0 && X, "hilo_model_rollout_dae: NULL argument");
+  HILO_REQUIRE(kf->nu + kf->np == 0 || up, "hilo_model_rollout_dae: the model has %d inputs/parameters but `up` is NULL", kf->nu + kf->np);
+  HILO_REQUIRE(up_stride == 0 || up_stride >= kf->nu + kf->np, "hilo_model_rollout_dae: up_stride %lld < nu+np", (long long)up_stride);
+  HILO_REQUIRE(up_step == 0 || up_step >= (up_stride ? batch * up_stride : kf->nu + kf->np),
+               "hilo_model_rollout_dae: up_step %lld is shorter than one sampling interval's rows", (long long)up_step);
+  HILO_HIP_CHECK(hipSetDevice(kf->device));
+  static const double zero = 0.0;
+  if (!up) up = &zero;   // never read (nu + np == 0); keeps the pointer arithmetic of the kernel defined
+  hipFunction_t fn = kf->jit.rollout_idas;
+  HILO_REQUIRE(fn, "hilo_model_rollout_dae: the run-time compiled roll-out kernel is not loaded");
+  KfParams kpv = kf->kp;
+  int* st = (int*)stats;
+  void* args[] = {&kpv, &sp, &batch, &steps, &x0, &z0, &up, &up_stride, &up_step, &X, &Z, &Y, &st};
+  const unsigned grid = (unsigned)((batch + ROLLOUT_TPB - 1) / ROLLOUT_TPB);
+  HILO_HIP_CHECK(hipModuleLaunchKernel(fn, grid, 1, 1, ROLLOUT_TPB, 1, 1, 0, (hipStream_t)stream, args, nullptr));
+  return HILO_OK;
 }
 
 extern "C" int hilo_model_rollout_resume(hilo_kf* kf, const hilo_sim_opts* opts, int64_t batch, int steps, const double* x0,

@@ -37,7 +37,8 @@ ZOO_FUNCTOR = {'toy1d': 'Toy1D', 'bioreactor3': 'Bioreactor3', 'chemostat4': 'Ch
 MODEL_USER = 100    # HILO_MODEL_USER: the model is defined by expressions and compiled at setup (csrc/hilo_jit.hip)
 # `Model.setup(solver=...)`: integrators with error control and their options under CasADi's names (what the reference's
 # `solver_options` carries to `ca.integrator`), with CasADi's defaults for CVODES
-SOLVERS = {'dopri5': 1, 'bdf': 2}  # name -> hilo_sim_opts.method (HILO_SIM_DOPRI5, HILO_SIM_BDF)
+SOLVERS = {'dopri5': 1, 'bdf': 2, 'idas': 3}  # name -> hilo_sim_opts.method (HILO_SIM_DOPRI5, HILO_SIM_BDF, HILO_SIM_IDAS)
+IDAS_MAX_STATES = 8  # n_x + n_z of a model under 'idas' (HILO_SIM_BDF_MAX_NX: the store of the method in the LDS of one workgroup)
 SOLVER_OPTIONS = {'reltol': 1e-6, 'abstol': 1e-8, 'max_num_steps': 10000, 'first_step': 0.}
 SIM_STATUS = {0: 'ok', 1: 'max_num_steps reached', 2: 'step size too small'}     # HILO_SIM_STATUS_*
 
@@ -58,7 +59,7 @@ class Model:
     For `Model('lti', A=..., B=..., C=...)` the matrices define a discrete LTI system
     (`x+ = A x + B u`, `y = C x`, cf. tests/test_LMPC.py:8-19)."""
 
-    _solver = None              # `setup(solver=...)`: None = the fixed-step maps, 'dopri5' / 'bdf' = integration with error control
+    _solver = None              # `setup(solver=...)`: None = the fixed-step maps, 'dopri5' / 'bdf' / 'idas' = integration with error control
     _solver_options = None
 
     def __init__(self, name=None, A=None, B=None, C=None, discrete=None, id=None, plot_backend=None, **kwargs):
@@ -558,6 +559,11 @@ class Model:
         stability and takes thousands of steps per interval or ends with 'max_num_steps reached'.  With inputs held over a
         `rollout` the integrator's state is carried across the sampling instants (their states are interpolated, only the end
         clips a step); with an input sequence every interval starts afresh.  Models of up to 8 states.
+        'idas' is the same method for a model WITH algebraic states, dx/dt = f(x, z, u, p), 0 = g(x, z, u, p), where the reference
+        integrates with IDAS: the formulas are applied to the combined vector [x; z] (the algebraic equations are rows of the Newton
+        system, not a nested iteration per evaluation; the error test sees z as well), z is made consistent at the start and
+        whenever the inputs jump, and `rollout(..., return_z=True)` / `solution['z']` give the algebraic states at the sampling
+        instants.  Models of up to 8 differential and algebraic states together.
         solver_options, under CasADi's names (defaults: CasADi's for CVODES): reltol 1e-6, abstol 1e-8, max_num_steps 10000
         (attempted steps per sampling interval), first_step 0 (estimated)."""
         if self._symbolic and self._ode is None:
@@ -576,7 +582,14 @@ class Model:
                 raise RuntimeError("Model is discrete. No solver is required.")
             if solver not in SOLVERS:
                 raise ValueError(f"Solver '{solver}' is not available on your system. Use 'dopri5' instead, or 'bdf' for a stiff model")
-            if getattr(self, 'n_z', 0):
+            if solver == 'idas':
+                if not getattr(self, 'n_z', 0):
+                    raise RuntimeError(f"Solver 'idas' integrates a model with algebraic states; model '{self.name}' has none. Use "
+                                       f"'bdf' for a stiff model, or 'dopri5'")
+                if self.n_x + self.n_z > IDAS_MAX_STATES:
+                    raise NotImplementedError(f"Solver 'idas' is built for at most {IDAS_MAX_STATES} differential and algebraic states "
+                                              f"together; model '{self.name}' has {self.n_x} + {self.n_z}")
+            elif getattr(self, 'n_z', 0):
                 raise RuntimeError(f"Solver '{solver}' is not suitable for DAE systems. Use 'idas' or 'collocation' instead")
             opts = dict(SOLVER_OPTIONS)
             for k, v in (solver_options or {}).items():
@@ -836,14 +849,20 @@ class Model:
         xn, y = xn[:, 0], y[:, 0]
         return (xn.cpu().numpy(), y.cpu().numpy()) if host else (xn, y)
 
-    def rollout(self, x0, u=None, p=None, steps=1, return_stats=False, device_index=None, t0=0., _h=None):
+    def rollout(self, x0, u=None, p=None, steps=1, return_stats=False, device_index=None, t0=0., _h=None, z0=None, return_z=False):
         """The many-interval sibling of `step`: `steps` sampling intervals for a batch of states in ONE launch
         (`hilo_model_rollout`), with the model's own map or, after `setup(solver='dopri5')` or `'bdf'`, under error control.
 
         x0 [B, n_x]; u [B, n_u] held over the roll-out or [steps, B, n_u] one row per sampling interval, p likewise; a batch axis
         of 1 is shared by the batch.  Returns x [steps + 1, B, n_x] (x[0] = x0) and y [steps, B, n_y] with y[k] = h(x[k + 1], u[k], p)
         - device tensors for device tensors (no host copy), numpy for numpy - and with return_stats a dict of per-instance arrays
-        'status' (0 ok, 1 max_num_steps reached, 2 step size too small), 'n_accepted', 'n_rejected', 'n_rhs'.  The rows of an instance
+        'status' (0 ok, 1 max_num_steps reached, 2 step size too small, 3 - 'idas' alone - no consistent algebraic states found: the
+        Newton iteration on g = 0 did not converge, dg/dz is singular or a value is not finite; at the start, at a jump of the inputs
+        or at any sampling instant, where the interpolated z is corrected onto g = 0), 'n_accepted', 'n_rejected', 'n_rhs'.
+        Under `setup(solver='idas')`: z0 [B, n_z], or one row for the batch, is where the Newton iteration for the consistent initial
+        algebraic states starts (None: the guess compiled into the model, `user_source(z_guess=)`; zeros unless one was given); with return_z a further output z [steps + 1, B, n_z] follows y - the algebraic states at
+        the sampling instants, z[0] the consistent initial values - and y[k] = h(x[k + 1], z[k + 1], u[k], p).  Either with another
+        solver is a ValueError.  The rows of an instance
         whose integration failed are NaN from the sampling instant it did not reach.  Allocates its outputs; inputs AND
         parameters together are packed into one buffer that is kept for the next call - calls on one model must therefore be
         ordered on one stream (the current stream of the device at the time of the call): a second call rewrites the buffer.
@@ -865,6 +884,10 @@ class Model:
         steps = int(steps)
         if steps < 1:
             raise ValueError(f"steps must be at least 1, got {steps}")
+        idas = self._solver == 'idas'
+        if (z0 is not None or return_z) and not idas:
+            raise ValueError("z0 and return_z belong to solver='idas' (Model.setup); this model is simulated " +
+                             (f"with solver '{self._solver}'" if self._solver else "with its fixed-step map"))
         h = self._plant_handle(device_index)
         dev = h._dev
         host = not isinstance(x0, torch.Tensor)
@@ -906,7 +929,17 @@ class Model:
             o = self._solver_options
             opts.method, opts.max_steps = SOLVERS[self._solver], o['max_num_steps']
             opts.rtol, opts.atol, opts.h0 = o['reltol'], o['abstol'], o['first_step']
-        if _h is not None and self._solver == 'dopri5':
+        if idas:
+            zt = None
+            if z0 is not None:
+                zt = to_dev(z0, dev).reshape(-1, self.n_z)
+                if zt.shape[0] not in (1, B):
+                    raise ValueError(f"a z0 of {zt.shape[0]} rows does not match {B} states")
+                zt = zt.expand(B, -1).contiguous()
+            Z = torch.empty(steps + 1, B, self.n_z, dtype=torch.float64, device=dev) if return_z else None
+            _lib.check(_lib.lib().hilo_model_rollout_dae(h._handle, ctypes.byref(opts), B, steps, ptr(xt), ptr(zt), ptr(up), up_stride,
+                                                         up_step, ptr(X), ptr(Z), ptr(Y), ptr(stats), stream_ptr(dev)))
+        elif _h is not None and self._solver == 'dopri5':
             if _h[0] is None or _h[0].shape != (B,) or _h[0].device != xt.device:
                 _h[0] = torch.zeros(B, dtype=torch.float64, device=dev)
             _lib.check(_lib.lib().hilo_model_rollout_resume(h._handle, ctypes.byref(opts), B, steps, ptr(xt), ptr(up), up_stride, up_step,
@@ -915,6 +948,8 @@ class Model:
             _lib.check(_lib.lib().hilo_model_rollout(h._handle, ctypes.byref(opts), B, steps, ptr(xt), ptr(up), up_stride, up_step, ptr(X),
                                                      ptr(Y), ptr(stats), stream_ptr(dev)))
         out = (X.cpu().numpy(), Y.cpu().numpy()) if host else (X, Y)
+        if return_z:
+            out += (Z.cpu().numpy() if host else Z,)
         if return_stats:
             st = stats.cpu().numpy() if host else stats
             out += ({'status': st[:, 0], 'n_accepted': st[:, 1], 'n_rejected': st[:, 2], 'n_rhs': st[:, 3]},)
@@ -931,6 +966,15 @@ class Model:
             raise ValueError(f"Dimension mismatch. Supplied dimension for the initial states is {x.shape[1]}, but required "
                              f"dimension is {self.n_x}.")
         self._sim = {'t': [float(t0)], 'x': [x], 'y': [], 'u': [], 'status': [], 'n_accepted': [], 'n_rejected': []}
+        if z0 is not None and getattr(self, 'n_z', 0):
+            # where `simulate` under solver='idas' starts the Newton iteration for the consistent algebraic states of the first call
+            z = np.atleast_2d(np.asarray(z0.cpu() if hasattr(z0, 'cpu') else z0, dtype=float))
+            if z.shape[1] != self.n_z:
+                z = z.T
+            if z.shape[1] != self.n_z or z.shape[0] not in (1, x.shape[0]):
+                raise ValueError(f"Dimension mismatch. Supplied dimension for the initial algebraic states is {z.shape[1]}, but "
+                                 f"required dimension is {self.n_z}.")
+            self._sim['_z0'] = z
 
     def simulate(self, u=None, p=None, steps=1, tf=None, **kwargs):
         """dynamic_model.py:3911-4000: advance the stored state by `steps` sampling intervals (or up to `tf`: int(tf / dt) of them,
@@ -941,7 +985,8 @@ class Model:
         give what one `rollout` over all of them gives.  Without a solver and with inputs / parameters of at most two dimensions this is a loop over `step`.  With
         `setup(solver=...)`, or with a sequence u [steps, B, n_u] (p likewise; `steps` is then taken from it), it is ONE `rollout`;
         `solution['status']`, `['n_accepted']`, `['n_rejected']` hold the integrator's per-instance status and step counts of each
-        call."""
+        call.  Under 'idas' `solution['z']` / `['z:f']` hold the algebraic states, shaped like x; the first call starts the Newton
+        iteration for the consistent initial values at the z0 of `set_initial_conditions`, every later one at the stored z."""
         if not self._is_setup:
             raise RuntimeError("Model is not set up. Run Model.setup() before running simulations.")
         if getattr(self, '_sim', None) is None:
@@ -961,7 +1006,15 @@ class Model:
             # a time-variant model goes on with the step sizes of its last call: two calls equal one roll-out over both stretches
             # (an autonomous model's calls each estimate their first step, as they always did)
             keep = self._sim.setdefault('_h', [None]) if self.is_time_variant() else None
-            x, y, st = self.rollout(self._sim['x'][-1], u, p, steps=steps, return_stats=True, t0=self._sim['t'][-1], _h=keep)
+            if self._solver == 'idas':
+                # from the stored z of the last call, else the caller's z0; the first call records the consistent initial values
+                zs = self._sim.setdefault('z', [])
+                x, y, z, st = self.rollout(self._sim['x'][-1], u, p, steps=steps, return_stats=True, t0=self._sim['t'][-1],
+                                           z0=zs[-1] if zs else self._sim.get('_z0'), return_z=True)
+                zs[:] = zs or [z[0]]
+                zs.extend(z[1:])
+            else:
+                x, y, st = self.rollout(self._sim['x'][-1], u, p, steps=steps, return_stats=True, t0=self._sim['t'][-1], _h=keep)
             for k in range(int(steps)):
                 self._sim['x'].append(x[k + 1]), self._sim['y'].append(y[k])
                 self._sim['u'].append(u if u is None or u.ndim < 3 else u[k])

@@ -227,6 +227,26 @@ int hilo_model_rollout(hilo_kf* kf, const hilo_sim_opts* opts, int64_t batch, in
 int hilo_model_rollout_resume(hilo_kf* kf, const hilo_sim_opts* opts, int64_t batch, int steps, const double* x0,
                               const double* up, int64_t up_stride, int64_t up_step, double* X, double* Y, int32_t* stats,
                               double* h, void* stream);
+/* The roll-out of a model with algebraic states, dx/dt = f(x, z, u, p), 0 = g(x, z, u, p) (semi-explicit, index 1), under
+   HILO_SIM_IDAS: variable-order (1..5) backward differentiation formulas in the combined vector [x; z], where the reference
+   integrates such a model with IDAS (csrc/hilo_integrate.h::idas_interval: the method of HILO_SIM_BDF, the algebraic rows of the
+   Newton system unscaled, the error test over all components).  opts->method must be HILO_SIM_IDAS; the other fields as above
+   (t0 is not read: such a model does not name the time).
+     z0 [B][nz] or NULL: where the Newton iteration for the consistent initial z starts (NULL: the guess compiled into the model);
+     Z [steps+1][B][nz] or NULL: the algebraic states at the sampling instants, row 0 the consistent initial values;
+     Y [steps][B][ny] = h(x_{k+1}, z_{k+1}, u_k, p) on the pair written to X and Z;  every other argument as for hilo_model_rollout.
+   At the start, and with an input sequence at every sampling instant, z is made consistent by Newton's method (at most 40 sweeps);
+   an instance for which that fails - no convergence, a singular dg/dz, a non-finite value - ends with
+   HILO_SIM_STATUS_IC_FAILED.  The same status ends an instance at ANY sampling instant at which the correction of the interpolated z
+   onto g(x, z) = 0 - the same iteration with the same exit test, residual at most 1e-13 (1 + |z|) - does not get there, for
+   instance with a badly scaled g; its rows are NaN from that instant on.  Rows of X, Z and Y from the first instant an instance did not reach are NaN (a failure at the very
+   start: from row 1 of X and row 0 of Z).  HILO_ENOTSUP for a handle whose model has no algebraic states, for nx + nz >
+   HILO_SIM_BDF_MAX_NX, for a kernel that needs scratch memory and for a method other than HILO_SIM_IDAS. */
+#define HILO_SIM_IDAS 3
+#define HILO_SIM_STATUS_IC_FAILED 3
+int hilo_model_rollout_dae(hilo_kf* kf, const hilo_sim_opts* opts, int64_t batch, int steps, const double* x0,
+                           const double* z0 /* [batch][nz] or NULL */, const double* up, int64_t up_stride, int64_t up_step,
+                           double* X, double* Z /* [steps+1][batch][nz] or NULL */, double* Y, int32_t* stats, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------- */
 /* Linear-quadratic regulator: batched linearisation, Riccati gains and feedback                            */
