@@ -698,6 +698,45 @@ extern "C" int hilo_nmpc_plant_step(hilo_nmpc* h, int64_t batch, const double* x
   return HILO_OK;
 }
 
+// Developer aid: one wave runs the engine's n-value wave reduction (WaveReduceN) in its transposing and in its plain form on the
+// same 64 x n lane values (in[lane * n + j]); out_new[n], out_plain[n].  The operation mixes are compiled in: those of the engine's
+// call sites and a few more per n.
+template <int... OPS>
+__global__ void __launch_bounds__(64) reduce_selftest_kernel(const double* in, double* out_new, double* out_plain) {
+  constexpr int n = sizeof...(OPS);
+  double a[n], b[n];
+  for (int j = 0; j < n; ++j) a[j] = b[j] = in[threadIdx.x * n + j];
+  WaveReduceN<OPS...>::run_transposed(a);
+  WaveReduceN<OPS...>::run_plain(b);
+  if (threadIdx.x == 0)
+    for (int j = 0; j < n; ++j) { out_new[j] = a[j]; out_plain[j] = b[j]; }
+}
+template <int... OPS>
+static bool reduce_selftest_try(int n, const int* ops, const double* in, double* out_new, double* out_plain, hipStream_t s) {
+  constexpr int want[] = {OPS...};
+  if (n != (int)sizeof...(OPS)) return false;
+  for (int j = 0; j < n; ++j)
+    if (ops[j] != want[j]) return false;
+  hipLaunchKernelGGL((reduce_selftest_kernel<OPS...>), dim3(1), dim3(64), 0, s, in, out_new, out_plain);
+  return true;
+}
+extern "C" int hilo_ocp_reduce_selftest(int n, const int* ops, const double* in, double* out_new, double* out_plain, void* stream) {
+  HILO_REQUIRE(n >= 1 && n <= 8 && ops && in && out_new && out_plain, "hilo_ocp_reduce_selftest: bad argument");
+  hipStream_t s = (hipStream_t)stream;
+  constexpr int S = R_SUM, M = R_MAX, I = R_MIN, P = R_MAX2;
+#define T(...) reduce_selftest_try<__VA_ARGS__>(n, ops, in, out_new, out_plain, s)
+  const bool ok = T(S) || T(M) || T(I) || T(P) ||
+                  T(S, S) || T(M, M) || T(I, M) || T(S, P) ||
+                  T(S, S, S) || T(M, M, S) || T(I, S, P) ||
+                  T(S, S, S, S) || T(P, I, M, M) || T(S, M, I, P) ||
+                  T(S, P, I, M, M, S, S) || T(S, S, S, S, S, S, S) ||
+                  T(S, S, S, S, S, S, S, S) || T(S, P, I, M, M, S, S, M) || T(M, P, M, I, P, M, I, M);
+#undef T
+  if (!ok) return fail(HILO_EINVAL, "hilo_ocp_reduce_selftest: this mix of %d operations is not compiled in", n);
+  HILO_HIP_CHECK(hipGetLastError());
+  return HILO_OK;
+}
+
 #ifdef HILO_OCP_DPROF
 extern "C" int hilo_debug_dprof(long long* out, int reset) {
   if (out) HILO_HIP_CHECK(hipMemcpyFromSymbol(out, HIP_SYMBOL(hilo::g_dprof), sizeof(long long) * 32));

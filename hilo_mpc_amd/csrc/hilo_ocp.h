@@ -38,9 +38,10 @@ constexpr int OCP_MAXNC = 16;  // nonlinear inequality rows per stage (stage row
 #define OCP_PHASE __attribute__((noinline))
 #endif
 // developer knob, all on in the product: the seams of the iteration that can be built out one by one to measure them (bit 0: cost
-// section of eval_derivs_sym without conditional reads, bit 1: defects copied by the update)
+// section of eval_derivs_sym without conditional reads, bit 1: defects copied by the update, bit 2: transposing form of WaveReduceN,
+// bit 3: filter acceptance by one ballot)
 #ifndef HILO_OCP_SEAMS
-#define HILO_OCP_SEAMS 3
+#define HILO_OCP_SEAMS 15
 #endif
 constexpr int OCP_SEAMS = HILO_OCP_SEAMS;
 // build-out knob of the layout pass: -DHILO_OCP_LAYOUT_CAP=0 launches the precompiled tracking policies with the run-time LDS
@@ -205,6 +206,21 @@ __device__ __forceinline__ double red_apply(int op, double a, double b) {
     default: return fmax(a, b);
   }
 }
+// The transposing form (OCP_SEAMS bit 2) walks the same pairing tree - xor 1, xor 2, half-mirror, mirror, then (r0 o r16) o (r32 o r48) -
+// but a lane does not carry every value through every level.  The values are sorted by operation into groups of up to four (sums;
+// maxima, with a minimum as the negated maximum of the negated values: a sign flip is exact and fmin(a, b) = -fmax(-a, -b) bit for
+// bit, +-0 included).  At xor 1 a lane keeps one half of its group and sends the other half to its partner, at xor 2 the halves split
+// again: from there on one value per lane, and each further level is one move pair and one operation for the whole group.  Which
+// half a lane keeps: b0 = bit 0 ^ bit 2 and b1 = bit 1 ^ bit 2 of the lane number, not bits 0 and 1 themselves - the two mirror
+// levels pair lane l with l ^ 7 and l ^ 15, whose low bits are flipped together with bit 2, so that b0 and b1 agree in both
+// partners.  The two row levels swap rows through v_permlane16_swap / v_permlane32_swap (two register copies, the two swaps and
+// one operation for the group; the operands arrive as (r0, r16) and (r0 o r16, r32 o r48), the order of the plain form); at the
+// end each value is read once from the lane of row 0 that owns it.  Only WHICH lane holds a partial differs from the plain form,
+// and in half of the links the operands change sides: +, v_max_f64 and v_min_f64 commute bit for bit for everything but two
+// NaNs of different payload, which no reduced value can tell apart (R_MAX: the vote in front of the levels decides, as before;
+// the sums only ask whether the result is a NaN).  The zero-sign argument above wave_any_nan is about v_max_f64 against nmax and
+// holds unchanged: the links are the same v_max_f64 on the same pairs.
+typedef unsigned ocp_u2 __attribute__((ext_vector_type(2)));
 template <int... OPS>
 struct WaveReduceN {
   static constexpr int n = sizeof...(OPS);
@@ -217,7 +233,8 @@ struct WaveReduceN {
 #pragma unroll
     for (int j = 0; j < n; ++j) v[j] = red_apply(ops[j], v[j], t[j]);
   }
-  __device__ __forceinline__ static void run(double* v) {
+  // the plain form: every lane carries all n values through the four in-row levels, row totals through v_readlane
+  __device__ __forceinline__ static void run_plain(double* v) {
     static_assert(OCP_TPB == 64, "one wave per instance");
     constexpr int ops[n] = {OPS...};
     bool nan[n];
@@ -239,6 +256,87 @@ struct WaveReduceN {
       v[j] = nan[j] ? __builtin_nan("") : r;
     }
   }
+  template <bool SUM>
+  __device__ __forceinline__ static double gop(double a, double b) { return SUM ? a + b : fmax(a, b); }
+  template <bool SUM, int CTRL>
+  __device__ __forceinline__ static double link(double keep, double send) { return gop<SUM>(keep, dpp_mov<CTRL>(send)); }
+  template <bool SUM, bool ROW32>
+  __device__ __forceinline__ static double row_link(double w) {
+    const unsigned lo = (unsigned)__double2loint(w), hi = (unsigned)__double2hiint(w);
+    const ocp_u2 a = ROW32 ? __builtin_amdgcn_permlane32_swap(lo, lo, false, false) : __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
+    const ocp_u2 b = ROW32 ? __builtin_amdgcn_permlane32_swap(hi, hi, false, false) : __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+    return gop<SUM>(__hiloint2double((int)b.x, (int)a.x), __hiloint2double((int)b.y, (int)a.y));
+  }
+  // one group of C <= 4 values under one operation; g[k] returns wave-uniform
+  template <bool SUM, int C>
+  __device__ __forceinline__ static void group(double* g, bool b0, bool b1) {
+    static_assert(C >= 1 && C <= 4, "groups of up to four values");
+    double w;
+    if constexpr (C == 1) {
+      w = link<SUM, 0xB1>(g[0], g[0]);
+      w = link<SUM, 0x4E>(w, w);
+    } else if constexpr (C == 2) {   // value b0
+      w = link<SUM, 0xB1>(b0 ? g[1] : g[0], b0 ? g[0] : g[1]);
+      w = link<SUM, 0x4E>(w, w);
+    } else {                         // value 2 b0 + b1 (C == 3: lanes with b0 && b1 carry value 1 once more)
+      const double w0 = link<SUM, 0xB1>(b0 ? g[2] : g[0], b0 ? g[0] : g[2]);
+      const double w1 = C == 4 ? link<SUM, 0xB1>(b0 ? g[3] : g[1], b0 ? g[1] : g[3]) : link<SUM, 0xB1>(g[1], g[1]);
+      w = link<SUM, 0x4E>(b1 ? w1 : w0, b1 ? w0 : w1);
+    }
+    w = link<SUM, 0x141>(w, w);
+    w = link<SUM, 0x140>(w, w);
+    w = row_link<SUM, false>(w);
+    w = row_link<SUM, true>(w);
+    // owner of value k in row 0: the lane of quad 0 (bit 2 clear) with b0, b1 as above
+    if constexpr (C <= 2) {
+#pragma unroll
+      for (int k = 0; k < C; ++k) g[k] = read_lane(w, k);
+    } else {
+#pragma unroll
+      for (int k = 0; k < C; ++k) g[k] = read_lane(w, (k >> 1) | ((k & 1) << 1));
+    }
+  }
+  template <bool SUM>
+  __device__ __forceinline__ static void groups(double* v, bool b0, bool b1) {
+    constexpr int ops[n] = {OPS...};
+    int idx[n] = {};
+    int c = 0;
+#pragma unroll
+    for (int j = 0; j < n; ++j)
+      if ((ops[j] == R_SUM) == SUM) idx[c++] = j;
+#pragma unroll
+    for (int base = 0; base < n; base += 4) {
+      double g[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (base + k < c) g[k] = ops[idx[base + k]] == R_MIN ? -v[idx[base + k]] : v[idx[base + k]];
+      const int left = c - base;
+      if (left >= 4) group<SUM, 4>(g, b0, b1);
+      else if (left == 3) group<SUM, 3>(g, b0, b1);
+      else if (left == 2) group<SUM, 2>(g, b0, b1);
+      else if (left == 1) group<SUM, 1>(g, b0, b1);
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (base + k < c) v[idx[base + k]] = ops[idx[base + k]] == R_MIN ? -g[k] : g[k];
+    }
+  }
+  __device__ __forceinline__ static void run_transposed(double* v) {
+    static_assert(OCP_TPB == 64, "one wave per instance");
+    constexpr int ops[n] = {OPS...};
+    bool nan[n];
+#pragma unroll
+    for (int j = 0; j < n; ++j) nan[j] = ops[j] == R_MAX && wave_any_nan(v[j]);
+    const unsigned t = threadIdx.x;
+    const bool b0 = ((t ^ (t >> 2)) & 1u) != 0, b1 = ((t ^ (t >> 1)) & 2u) != 0;
+    groups<true>(v, b0, b1);
+    groups<false>(v, b0, b1);
+#pragma unroll
+    for (int j = 0; j < n; ++j) v[j] = nan[j] ? __builtin_nan("") : v[j];
+  }
+  __device__ __forceinline__ static void run(double* v) {
+    if constexpr (OCP_SEAMS & 4) run_transposed(v);
+    else run_plain(v);
+  }
 };
 
 template <class Op>
@@ -253,6 +351,27 @@ __device__ __forceinline__ double block_reduce(double v, __attribute__((address_
   double r = Op::id();
   for (int w = 0; w < nw; ++w) r = Op::f(r, scratch[w]);
   return r;
+}
+
+// Is the point (th, ph) dominated by an entry of the filter (pairs (theta, phi) in filt, nfilt <= 64 of them)?  MARGIN: with the
+// rounding allowance of the line search on phi.  An "any" over the entries: lane q tests entry q (the lanes beyond the filter
+// test entry 0 once more) and one ballot decides - one LDS round trip instead of one per entry in a serial loop.  th, ph and
+// nfilt are wave-uniform.
+template <bool MARGIN>
+__device__ __forceinline__ bool filter_dominates(const lds_double* filt, int nfilt, double th, double ph) {
+  if constexpr (OCP_TPB == 64 && (OCP_SEAMS & 8)) {
+    if (nfilt == 0) return false;
+    const int q = (int)threadIdx.x < nfilt ? (int)threadIdx.x : 0;
+    const double tf = filt[2 * q], pf = filt[2 * q + 1];
+    const bool hit = MARGIN ? (th >= tf && ph - 10 * 2.220446049250313e-16 * fabs(pf) >= pf) : (th >= tf && ph >= pf);
+    return __builtin_amdgcn_ballot_w64(hit) != 0ull;
+  } else {
+    for (int q = 0; q < nfilt; ++q) {
+      const double tf = filt[2 * q], pf = filt[2 * q + 1];
+      if (MARGIN ? (th >= tf && ph - 10 * 2.220446049250313e-16 * fabs(pf) >= pf) : (th >= tf && ph >= pf)) return true;
+    }
+    return false;
+  }
 }
 
 // optional members of a policy, with their defaults
@@ -2095,13 +2214,18 @@ struct Ocp {
     }
     // (scalings with reciprocals - v_rcp_f64 and two Newton steps, <= 1 ulp - instead of IEEE divisions: five dependent
     // 13-instruction sequences on wave-uniform values otherwise)
+    // Three of the five take inputs that are the same for the whole solve and do not wait for the reductions; the two that depend on
+    // the iterate, of s_d and s_c, do not depend on each other and are written side by side so that their Newton chains interleave.
+    // (Forming the three once per solve and holding them in scalar registers was measured and is not in: DESIGN.md 5.1.)
     const double i_smax = rcp_fast(pc.s_max);
     const double s_d = fmax(pc.s_max, (lsum + zsum) * rcp_fast(N * NX + ncon + nb)) * i_smax;
     // a NaN multiplier or defect must reach the error measure (fmax would drop it): through the sums
     const double poison = (lsum + zsum + r.theta) * 0.0;      // 0, or NaN
-    r.s_c = uni(fmax(pc.s_max, zsum * rcp_fast(nb)) * i_smax + poison);
-    r.i_s_c = uni(rcp_fast(r.s_c));
-    r.dual_s = uni(dmax * rcp_fast(s_d));
+    const double s_c = fmax(pc.s_max, zsum * rcp_fast(nb)) * i_smax + poison;
+    const double i_s_c = rcp_fast(s_c), i_s_d = rcp_fast(s_d);
+    r.s_c = uni(s_c);
+    r.i_s_c = uni(i_s_c);
+    r.dual_s = uni(dmax * i_s_d);
     r.prim = uni(pmax);
     DTICK(13)
     return r;
@@ -3327,10 +3451,7 @@ struct Ocp {
       th = tht;
       if (th <= 0.9 * th_start && th <= theta_max) {
         const double ph = ft + mu * barrier_logs(l, l.Z, l.cs);
-        bool acc = true;
-        for (int q = 0; q < nfilt; ++q)
-          if (th >= l.filt[2 * q] && ph >= l.filt[2 * q + 1]) { acc = false; break; }
-        if (acc) return 0;
+        if (!filter_dominates<false>(l.filt, nfilt, th, ph)) return 0;
       }
       eval_derivs(lbase, ws);
     }
@@ -3754,12 +3875,7 @@ __device__ __forceinline__ void ocp_solve_body(lds_double* lds_raw, const OcpCon
       const double ft = trial.f, tht = trial.theta;
       const double pht = uni(ft + mu * blog_t);
       bool ok = isfinite(pht) && isfinite(tht) && tht <= theta_max;
-      if (ok) {
-        for (int q = 0; q < nfilt; ++q) {
-          const double tf = l.filt[2 * q], pf = l.filt[2 * q + 1];
-          if (tht >= tf && pht - 10 * 2.220446049250313e-16 * fabs(pf) >= pf) { ok = false; break; }
-        }
-      }
+      if (ok) ok = !filter_dominates<true>(l.filt, nfilt, tht, pht);
       bool sw = false;
       if (ok) {
         sw = th0 <= theta_min && dphi < 0.0 && S::switching(pc, alpha, -dphi, th0);
@@ -3810,12 +3926,7 @@ __device__ __forceinline__ void ocp_solve_body(lds_double* lds_raw, const OcpCon
           const double ths = t2.theta;
           const double phs = uni(t2.f + mu * blog_t);
           bool oks = isfinite(phs) && isfinite(ths) && ths <= theta_max;
-          if (oks) {
-            for (int q = 0; q < nfilt; ++q) {
-              const double tf = l.filt[2 * q], pf = l.filt[2 * q + 1];
-              if (ths >= tf && phs - 10 * 2.220446049250313e-16 * fabs(pf) >= pf) { oks = false; break; }
-            }
-          }
+          if (oks) oks = !filter_dominates<true>(l.filt, nfilt, ths, phs);
           if (oks) {
             const bool sw2 = th0 <= theta_min && dphi < 0.0 && S::switching(pc, alpha, -dphi, th0);
             const double rnd = 10 * 2.220446049250313e-16 * fabs(phi0);

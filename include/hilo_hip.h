@@ -591,6 +591,10 @@ int hilo_nmpc_profile(hilo_nmpc* h, int enable, long long* cycles_host);
    on a kernel whose array offsets are compile-time constants and request lds_cap bytes; lds_next: the footprint at n_cap + 1.
    Needs no device. */
 int hilo_nmpc_layout_capacity(int model_id, int taylor, int* n_cap, long long* lds_cap, long long* lds_next);
+/* developer aid: one wave runs the interior-point engine's n-value wave reduction in its transposing and its plain form on the
+   same lane values.  n in 1..8; ops[n] (host): 0 sum, 1 NaN-propagating maximum, 2 minimum, 3 plain maximum - only the mixes
+   compiled in are accepted (HILO_EINVAL otherwise); in[64][n], out_new[n], out_plain[n] device memory */
+int hilo_ocp_reduce_selftest(int n, const int* ops, const double* in, double* out_new, double* out_plain, void* stream);
 /* x+ = Phi(x, u, p) with the controller's own shooting map: closed-loop harness (control_loop.py:343-396) */
 int hilo_nmpc_plant_step(hilo_nmpc* h, int64_t batch, const double* x, const double* u, const double* p,
                          int64_t p_stride, double* x_next, void* stream);
