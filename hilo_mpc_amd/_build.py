@@ -8,7 +8,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libhilo_hip.so')
 SOURCES = ['hilo_api.hip', 'hilo_kf.hip', 'hilo_sim.hip', 'hilo_lqr.hip', 'hilo_gp.hip', 'hilo_ann.hip', 'hilo_nmpc.hip', 'hilo_qp.hip', 'hilo_mhe.hip',
-           'hilo_nmpc_gen_chemostat4.hip', 'hilo_nmpc_gen_robot6.hip', 'hilo_nmpc_coll.hip', 'hilo_nmpc_tv.hip', 'hilo_mhe_est.hip', 'hilo_nmpc_long.hip', 'hilo_jit.hip', 'hilo_nmpc_user.hip']
+           'hilo_nmpc_gen_chemostat4.hip', 'hilo_nmpc_gen_robot6.hip', 'hilo_nmpc_coll.hip', 'hilo_nmpc_tv.hip', 'hilo_mhe_est.hip', 'hilo_nmpc_long.hip', 'hilo_jit.hip', 'hilo_nmpc_user.hip',
+           'hilo_selftest.hip']
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-fno-gpu-rdc', '-Wno-unused-result'] + \
     os.environ.get('HILO_EXTRA_FLAGS', '').split()      # developer knob (tuning sweeps), empty in normal builds
 # Translation units built around the interior-point engine (csrc/hilo_ocp.h): the f64 matrix-core products of its Riccati stage take

@@ -130,6 +130,9 @@ def _declare(lib):
         'hilo_nmpc_profile': (C.c_int, [vp, i32, vp]),
         'hilo_nmpc_layout_capacity': (C.c_int, [i32, i32, P(C.c_int), P(C.c_longlong), P(C.c_longlong)]),
         'hilo_ocp_reduce_selftest': (C.c_int, [i32, P(C.c_int), vp, vp, vp, vp]),
+        'hilo_ad_selftest': (C.c_int, [i64, vp, vp, vp]),
+        'hilo_expr_selftest': (C.c_int, [P(C.c_double), i32, i32, i32, i64, vp, vp, vp, vp]),
+        'hilo_jit_probe': (C.c_int, [C.c_char_p, i32, i32, i32, i32, i32, i64, vp, vp, vp, vp]),
         'hilo_nmpc_plant_step': (C.c_int, [vp, i64, vp, vp, vp, i64, vp, vp]),
         'hilo_jit_precompile': (C.c_int, [C.c_char_p] + [i32] * 11),
         'hilo_nmpc_set_aux_outputs': (C.c_int, [vp, vp, vp]),

@@ -16,7 +16,7 @@ from .expr import Expr
 
 _BIN = {'add': '+', 'sub': '-', 'mul': '*', 'div': '/'}
 _FUN = {n: n for n in ('sq', 'sin', 'cos', 'exp', 'log', 'sqrt', 'log10', 'fabs', 'sign', 'asin', 'acos', 'atan', 'asinh', 'acosh',
-                       'atanh')}        # csrc/hilo_ad.h: one overload per scalar type
+                       'atanh', 'tanh', 'sech2')}        # csrc/hilo_ad.h: one overload per scalar type
 
 
 def _lit(v):

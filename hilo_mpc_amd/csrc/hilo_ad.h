@@ -128,6 +128,14 @@ template <int N> HD Dual<N> sq(const Dual<N>& a) { return chain(a, a.v * a.v, 2.
 // the rest of the reference's function table (hilo_mpc/util/parsing.py:36-58); non-smooth ones as CasADi differentiates them:
 // d|a| = sign(a) da, d sign(a) = 0
 HD double sgn_of(double v) { return v > 0.0 ? 1.0 : (v < 0.0 ? -1.0 : 0.0); }
+// tanh from expm1, without a branch: the library's tanh branches per lane on the size of its argument, and a model with tanh terms
+// brought the backend's join-block defect described at HILO_TRIG_CALLS above into run-time compiled solver units
+// (tools/check_exec_prologue.py), inlined and behind a call alike.  em = expm1(-2 |v|) lies in [-1, 0]: tanh |v| = -em / (2 + em),
+// exact at +-0 (signed), 1 once em = -1, about 2 ulp in between
+HD double tanh_of(double v) { const double em = ::expm1(-2.0 * ::fabs(v)); return ::copysign(-em / (2.0 + em), v); }
+// 1 - tanh(v)^2 = 4 E / (1 + E)^2 with E = exp(-2 |v|) <= 1: no overflow and no cancellation for any v (1 - t * t keeps an absolute
+// error of 1e-16 where the exact value is 4 exp(-2 |v|); exp(2 v) is inf from |v| = 354.9 on); 0 once E underflows
+HD double sech2_of(double v) { const double e = ::exp(-2.0 * ::fabs(v)), d = 1.0 + e; return 4.0 * e / (d * d); }
 template <int N> HD Dual<N> log10(const Dual<N>& a) { return chain(a, ::log10(a.v), 0.4342944819032518 / a.v); }
 template <int N> HD Dual<N> fabs(const Dual<N>& a) { return chain(a, ::fabs(a.v), sgn_of(a.v)); }
 template <int N> HD Dual<N> sign(const Dual<N>& a) { return chain(a, sgn_of(a.v), 0.0); }
@@ -137,6 +145,10 @@ template <int N> HD Dual<N> atan(const Dual<N>& a) { return chain(a, ::atan(a.v)
 template <int N> HD Dual<N> asinh(const Dual<N>& a) { return chain(a, ::asinh(a.v), 1.0 / ::sqrt(a.v * a.v + 1.0)); }
 template <int N> HD Dual<N> acosh(const Dual<N>& a) { return chain(a, ::acosh(a.v), 1.0 / ::sqrt(a.v * a.v - 1.0)); }
 template <int N> HD Dual<N> atanh(const Dual<N>& a) { return chain(a, ::atanh(a.v), 1.0 / (1.0 - a.v * a.v)); }
+// tanh is native (composed of exp(2 a) its value and derivatives are inf / inf = NaN for a > 354.9, the saturation term tanh(v / eps));
+// sech2 = 1 - tanh^2 is the function its derivative is written with (expr.py, symdiff.py), (sech2)' = -2 tanh sech2
+template <int N> HD Dual<N> tanh(const Dual<N>& a) { return chain(a, tanh_of(a.v), sech2_of(a.v)); }
+template <int N> HD Dual<N> sech2(const Dual<N>& a) { const double s = sech2_of(a.v); return chain(a, s, -2.0 * tanh_of(a.v) * s); }
 template <int N> HD Dual<N> atan2(const Dual<N>& y, const Dual<N>& x) {
   Dual<N> r; r.v = ::atan2(y.v, x.v);
   const double ir = 1.0 / (x.v * x.v + y.v * y.v);
@@ -150,8 +162,18 @@ template <int N> HD Dual<N> atan2(double y, const Dual<N>& x) { return atan2(Dua
 // ------------------------------------------------------------------------------------------------
 // Jet2: univariate Taylor coefficients along one direction: f(t) = v + a t + (b/2) t^2 (a = f', b = f'')
 // ------------------------------------------------------------------------------------------------
-// reciprocal for the Taylor arithmetic: v_rcp_f64 + two Newton steps (5 instructions, <= 1 ulp) instead of the 12-instruction
-// IEEE division sequence; a zero divisor gives NaN, which the line search rejects like inf
+// reciprocal for the Taylor arithmetic: v_rcp_f64 + two Newton steps (5 instructions) instead of the 12-instruction IEEE division
+// sequence.  Contract on the device, as measured on gfx950 (tests/test_ad_ops_gpu.py pins it):
+//   x and 1 / x normal              within 1 ulp of 1 / x (measured 0.5), a * rcp_fast(b) within 2 ulp of a / b (measured 1.26)
+//   x = +-0                         NaN (v_rcp gives +-inf, the Newton step is fma(-0, inf, 1)) - the IEEE quotient is +-inf
+//   x = +-inf                       NaN (v_rcp gives +-0, the Newton step is fma(-inf, 0, 1)) - the IEEE quotient is +-0:
+//                                   1 / (1 + exp(z)) is NaN here and 0 on the host once exp(z) overflows
+//   x = NaN                         NaN
+//   |x| <= 2^-1024 (denormal)       NaN where 1 / x overflows (the IEEE quotient is +-inf)
+//   2^-1024 < |x| < 2^-1022         within 1 ulp of 1 / x (every sample measured equals the IEEE quotient)
+//   |x| >= 2^1022 (1 / x denormal)  within one denormal spacing of 1 / x (every sample measured equals the IEEE quotient)
+// so: never a finite wrong number; every non-finite case is NaN, which the line search rejects like inf.  The host branch is the
+// IEEE reciprocal.
 HD double rcp_fast(double x) {
 #if defined(__HIP_DEVICE_COMPILE__)
   double r = __builtin_amdgcn_rcp(x);
@@ -199,6 +221,8 @@ HD FastD atan(FastD a) { return FastD(::atan(a.v)); }
 HD FastD asinh(FastD a) { return FastD(::asinh(a.v)); }
 HD FastD acosh(FastD a) { return FastD(::acosh(a.v)); }
 HD FastD atanh(FastD a) { return FastD(::atanh(a.v)); }
+HD FastD tanh(FastD a) { return FastD(tanh_of(a.v)); }
+HD FastD sech2(FastD a) { return FastD(sech2_of(a.v)); }
 HD FastD atan2(FastD y, FastD x) { return FastD(::atan2(y.v, x.v)); }
 HD FastD atan2(FastD y, double x) { return FastD(::atan2(y.v, x)); }
 HD FastD atan2(double y, FastD x) { return FastD(::atan2(y, x.v)); }
@@ -249,6 +273,12 @@ HD Jet2 atan(const Jet2& x) { const double r = 1.0 / (1.0 + x.v * x.v); return c
 HD Jet2 asinh(const Jet2& x) { const double r = 1.0 / ::sqrt(x.v * x.v + 1.0); return chain(x, ::asinh(x.v), r, -x.v * r * r * r); }
 HD Jet2 acosh(const Jet2& x) { const double r = 1.0 / ::sqrt(x.v * x.v - 1.0); return chain(x, ::acosh(x.v), r, -x.v * r * r * r); }
 HD Jet2 atanh(const Jet2& x) { const double r = 1.0 / (1.0 - x.v * x.v); return chain(x, ::atanh(x.v), r, 2.0 * x.v * r * r); }
+HD Jet2 tanh(const Jet2& x) { const double t = tanh_of(x.v), s = sech2_of(x.v); return chain(x, t, s, -2.0 * t * s); }
+// (sech2)'' = 2 s (2 t^2 - s) = 2 s (3 t^2 - 1)
+HD Jet2 sech2(const Jet2& x) {
+  const double t = tanh_of(x.v), s = sech2_of(x.v);
+  return chain(x, s, -2.0 * t * s, 2.0 * s * ::fma(3.0 * t, t, -1.0));
+}
 // f = atan2(y, x):  f' = n / r with n = x y' - y x', r = x^2 + y^2;  f'' = (n' r - n r') / r^2, n' = x y'' - y x'', r' = 2 (x x' + y y')
 HD Jet2 atan2(const Jet2& y, const Jet2& x) {
   const double r = x.v * x.v + y.v * y.v, ir = 1.0 / r, n = x.v * y.a - y.v * x.a;
@@ -281,6 +311,8 @@ HD double atan(double x) { return ::atan(x); }
 HD double asinh(double x) { return ::asinh(x); }
 HD double acosh(double x) { return ::acosh(x); }
 HD double atanh(double x) { return ::atanh(x); }
+HD double tanh(double x) { return tanh_of(x); }
+HD double sech2(double x) { return sech2_of(x); }
 HD double atan2(double y, double x) { return ::atan2(y, x); }
 HD double value(double x) { return x; }
 template <int N> HD double value(const Dual<N>& x) { return x.v; }

@@ -585,4 +585,140 @@ int jit_launch_coll_out(hipFunction_t f, const OcpConst* dev, int64_t batch, int
   return HILO_OK;
 }
 
+// ---- developer aid: a model given as source evaluated on its own, in every scalar type and through its generated derivative code ----
+// A small unit of its own (the user source, hilo_models.h, one kernel), apart from the filter unit.  Row of `in`:
+//   x[NX] u[NU] p[NP] dx[NX] du[NU] kb[NX] kby[NY]
+// row of `out` (NZ = NX + NU, NH = NZ (NZ + 1) / 2, NHX = NX (NX + 1) / 2):
+//   ode, meas in double | in FastD | Dual<NZ> seeded with the identity: d ode / d(x,u) [NX][NZ], d meas / d(x,u) [NY][NZ] |
+//   Jet2 along (dx, du): ode v a b [3][NX], meas v a b [3][NY] | ModelSym: jx [NX][NX], jh's J [NX][NZ], H [NH], mjh's y [NY],
+//   Jy [NY][NX], Hy [NHX] (left as they came where the model has no symbolic source or no measurement part; flags[0], flags[1])
+static const char* const PROBE_KERNEL = R"(
 }  // namespace hilo
+using namespace hilo;
+extern "C" __global__ __launch_bounds__(64) void hilo_user_probe(long long n, const double* __restrict__ in, double* __restrict__ out,
+                                                                int* __restrict__ flags) {
+  using M = UserModel;
+  constexpr int NX = M::NX, NU = M::NU, NP = M::NP, NY = M::NY, NZ = NX + NU, NH = NZ * (NZ + 1) / 2, NHX = NX * (NX + 1) / 2;
+  constexpr int NUE = NU > 0 ? NU : 1, NPE = NP > 0 ? NP : 1, NYE = NY > 0 ? NY : 1;
+  constexpr int IN = 3 * NX + 2 * NU + NP + NY;
+  constexpr int OUT = 5 * (NX + NY) + (NX + NY) * NZ + NX * NX + NX * NZ + NH + NY + NY * NX + NHX;
+  static_assert(NX == HILO_PROBE_NX && NU == HILO_PROBE_NU && NP == HILO_PROBE_NP && NY == HILO_PROBE_NY,
+                "the dimensions given to hilo_jit_probe are not those of the model source");
+  const long long i = (long long)blockIdx.x * 64 + threadIdx.x;
+  if (i == 0) {
+    flags[0] = ModelSym<M>::value ? 1 : 0;
+    flags[1] = ModelSym<M>::HAS_MEAS ? 1 : 0;
+  }
+  if (i >= n) return;
+  const double* q = in + i * IN;
+  double* o = out + i * OUT;
+  double x[NX], u[NUE], p[NPE], kb[NX], kby[NYE];
+  for (int c = 0; c < NX; ++c) { x[c] = q[c]; kb[c] = q[2 * NX + 2 * NU + NP + c]; }
+  for (int c = 0; c < NU; ++c) u[c] = q[NX + c];
+  for (int c = 0; c < NP; ++c) p[c] = q[NX + NU + c];
+  for (int c = 0; c < NY; ++c) kby[c] = q[3 * NX + 2 * NU + NP + c];
+  const double* dir = q + NX + NU + NP;
+  {
+    double f[NX], y[NYE];
+    M::ode(x, u, p, 0.0, f);
+    M::meas(x, u, p, 0.0, y);
+    for (int c = 0; c < NX; ++c) o[c] = f[c];
+    for (int c = 0; c < NY; ++c) o[NX + c] = y[c];
+    o += NX + NY;
+  }
+  {
+    FastD xf[NX], uf[NUE], f[NX], y[NYE];
+    for (int c = 0; c < NX; ++c) xf[c] = FastD(x[c]);
+    for (int c = 0; c < NU; ++c) uf[c] = FastD(u[c]);
+    M::ode(xf, uf, p, 0.0, f);
+    M::meas(xf, uf, p, 0.0, y);
+    for (int c = 0; c < NX; ++c) o[c] = f[c].v;
+    for (int c = 0; c < NY; ++c) o[NX + c] = y[c].v;
+    o += NX + NY;
+  }
+  {
+    Dual<NZ> xd[NX], ud[NUE], f[NX], y[NYE];
+    for (int c = 0; c < NX; ++c) { xd[c] = Dual<NZ>(x[c]); xd[c].d[c] = 1.0; }
+    for (int c = 0; c < NU; ++c) { ud[c] = Dual<NZ>(u[c]); ud[c].d[NX + c] = 1.0; }
+    M::ode(xd, ud, p, 0.0, f);
+    M::meas(xd, ud, p, 0.0, y);
+    for (int c = 0; c < NX; ++c)
+      for (int j = 0; j < NZ; ++j) o[c * NZ + j] = f[c].d[j];
+    for (int c = 0; c < NY; ++c)
+      for (int j = 0; j < NZ; ++j) o[(NX + c) * NZ + j] = y[c].d[j];
+    o += (NX + NY) * NZ;
+  }
+  {
+    Jet2 xj[NX], uj[NUE], f[NX], y[NYE];
+    for (int c = 0; c < NX; ++c) xj[c] = Jet2(x[c], dir[c], 0.0);
+    for (int c = 0; c < NU; ++c) uj[c] = Jet2(u[c], dir[NX + c], 0.0);
+    M::ode(xj, uj, p, 0.0, f);
+    M::meas(xj, uj, p, 0.0, y);
+    for (int c = 0; c < NX; ++c) { o[c] = f[c].v; o[NX + c] = f[c].a; o[2 * NX + c] = f[c].b; }
+    o += 3 * NX;
+    for (int c = 0; c < NY; ++c) { o[c] = y[c].v; o[NY + c] = y[c].a; o[2 * NY + c] = y[c].b; }
+    o += 3 * NY;
+  }
+  if constexpr (ModelSym<M>::value) {
+    double fx[NX * NX], J[NX * NZ], H[NH];
+    ModelSym<M>::jx(x, u, p, fx);
+    ModelSym<M>::jh(x, u, p, kb, J, H);
+    for (int c = 0; c < NX * NX; ++c) o[c] = fx[c];
+    for (int c = 0; c < NX * NZ; ++c) o[NX * NX + c] = J[c];
+    for (int c = 0; c < NH; ++c) o[NX * NX + NX * NZ + c] = H[c];
+    if constexpr (ModelSym<M>::HAS_MEAS) {
+      double* om = o + NX * NX + NX * NZ + NH;
+      double y[NYE], Jy[NYE * NX], Hy[NHX];
+      ModelSym<M>::mjh(x, u, p, kby, y, Jy, Hy);
+      for (int c = 0; c < NY; ++c) om[c] = y[c];
+      for (int c = 0; c < NY * NX; ++c) om[NY + c] = Jy[c];
+      for (int c = 0; c < NHX; ++c) om[NY + NY * NX + c] = Hy[c];
+    }
+  }
+}
+)";
+
+}  // namespace hilo
+
+extern "C" int hilo_jit_probe(const char* user_source, int trig_calls, int nx, int nu, int np, int ny, int64_t n, const double* in,
+                              double* out, int* flags, void* stream) {
+  using namespace hilo;
+  HILO_REQUIRE(user_source && user_source[0] && nx >= 1 && nu >= 0 && np >= 0 && ny >= 0 && n >= 1 && n <= (1 << 20) && in && out && flags,
+               "hilo_jit_probe: bad argument");
+  std::string tu = trig_calls ? "#define HILO_TRIG_CALLS 1\n" : "";
+  char dims[160];
+  snprintf(dims, sizeof(dims), "#define HILO_PROBE_NX %d\n#define HILO_PROBE_NU %d\n#define HILO_PROBE_NP %d\n#define HILO_PROBE_NY %d\n",
+           nx, nu, np, ny);
+  tu += dims;
+  tu += "#include \"hilo_models.h\"\nextern \"C\" { __device__ const double* hilo_user_gp[4]; }\nnamespace hilo {\n";
+  tu += user_source;
+  tu += PROBE_KERNEL;
+  std::vector<std::string> opts;
+  std::string key, cpath;
+  int rc = unit_key(tu, &opts, &key);
+  if (rc) return rc;
+  std::vector<char> code;
+  {
+    std::lock_guard<std::mutex> lock(g_mu);
+    rc = unit_code(tu, opts, key, code, &cpath);
+  }
+  if (rc) return rc;
+  if (getenv("HILO_JIT_COMPILE_ONLY")) return HILO_OK;
+  hipModule_t mod;
+  hipError_t e = hipModuleLoadData(&mod, code.data());
+  if (e != hipSuccess) {
+    unlink(cpath.c_str());
+    return fail(HILO_EHIP, "hipModuleLoadData of the run-time compiled probe failed: %s", hipGetErrorString(e));
+  }
+  hipFunction_t f = nullptr;
+  e = hipModuleGetFunction(&f, mod, "hilo_user_probe");
+  if (e == hipSuccess) {
+    long long nn = n;
+    void* args[] = {&nn, &in, &out, &flags};
+    e = hipModuleLaunchKernel(f, (unsigned)((n + 63) / 64), 1, 1, 64, 1, 1, 0, (hipStream_t)stream, args, nullptr);
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);     // the module is unloaded below
+  (void)hipModuleUnload(mod);
+  HILO_HIP_CHECK(e);
+  return HILO_OK;
+}

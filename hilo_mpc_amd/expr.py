@@ -22,7 +22,8 @@ STACK = 8
 class Expr:
     """Node of an expression tree: op in {'const','x','u','p','z','theta','t', binary / unary op names, 'gp','gpd','gpvar','gpk'}.
     Unary functions: sq sin cos exp log sqrt (device interpreter and compiled code) and - compiled code only - the rest of the
-    reference's table (util/parsing.py:36-58): log10 fabs sign asin acos atan asinh acosh atanh; binary: atan2."""
+    reference's table (util/parsing.py:36-58): log10 fabs sign asin acos atan asinh acosh atanh tanh (and sech2 = 1 - tanh^2, the
+    function tanh's derivative is written with); binary: atan2."""
     __slots__ = ('op', 'args', 'value', 'name', 'serial')
     _count = 0
 
@@ -159,8 +160,8 @@ def _unary(op):
 sin, cos, exp, log, sqrt = (_unary(n) for n in ('sin', 'cos', 'exp', 'log', 'sqrt'))
 # the rest of the reference's function table (util/parsing.py:36-58 -> ca.log10, ca.sign, ca.fabs, ca.asin, ...): native device
 # functions of the compiled code (csrc/hilo_ad.h), not of the postfix interpreter
-NATIVE_UNARY = ('log10', 'fabs', 'sign', 'asin', 'acos', 'atan', 'asinh', 'acosh', 'atanh')
-log10, fabs, sign, asin, acos, atan, asinh, acosh, atanh = (_unary(n) for n in NATIVE_UNARY)
+NATIVE_UNARY = ('log10', 'fabs', 'sign', 'asin', 'acos', 'atan', 'asinh', 'acosh', 'atanh', 'tanh', 'sech2')
+log10, fabs, sign, asin, acos, atan, asinh, acosh, atanh, tanh, sech2 = (_unary(n) for n in NATIVE_UNARY)
 arcsin, arccos, arctan, arsinh, arcosh, artanh = asin, acos, atan, asinh, acosh, atanh
 
 
@@ -188,19 +189,20 @@ def tan(a):
     return sin(a) / cos(a)
 
 
+# 0.5 * e -+ 0.5 / e, not 0.5 * (e -+ 1.0 / e): the same roundings, but the Taylor quotient forms twice its first coefficient, and
+# 2 / e leaves the range from a = -709.09 on although sinh and cosh are finite up to |a| = 709.78
 def sinh(a):
     e = exp(Expr.wrap(a))
-    return 0.5 * (e - 1.0 / e)
+    return 0.5 * e - 0.5 / e
 
 
 def cosh(a):
     e = exp(Expr.wrap(a))
-    return 0.5 * (e + 1.0 / e)
+    return 0.5 * e + 0.5 / e
 
 
-def tanh(a):
-    e2 = exp(2.0 * Expr.wrap(a))
-    return (e2 - 1.0) / (e2 + 1.0)
+# tanh is NOT composed: (exp(2a) - 1) / (exp(2a) + 1) is inf / inf = NaN, value and derivatives, for a > ln(DBL_MAX) / 2 = 354.9 - the
+# saturation term tanh(v / eps) gets there; native beside asinh (NATIVE_UNARY), its derivative sech2 = 1 - tanh^2 native as well
 
 
 class SymVector:
@@ -261,6 +263,8 @@ _D_UNARY = {
     'asinh': lambda a: 1.0 / sqrt(a * a + 1.0),
     'acosh': lambda a: 1.0 / sqrt(a * a - 1.0),
     'atanh': lambda a: 1.0 / (1.0 - a * a),
+    'tanh': lambda a: sech2(a),
+    'sech2': lambda a: -2.0 * (tanh(a) * sech2(a)),
 }
 
 

@@ -21,7 +21,8 @@ from .expr import Expr
 # numeric counterparts of the unary functions (constant folding, evaluate())
 _NUMERIC = {'sin': math.sin, 'cos': math.cos, 'exp': math.exp, 'log': math.log, 'sqrt': math.sqrt, 'log10': math.log10,
             'fabs': math.fabs, 'sign': lambda v: (v > 0) - (v < 0) + 0.0, 'asin': math.asin, 'acos': math.acos, 'atan': math.atan,
-            'asinh': math.asinh, 'acosh': math.acosh, 'atanh': math.atanh}
+            'asinh': math.asinh, 'acosh': math.acosh, 'atanh': math.atanh, 'tanh': math.tanh,
+            'sech2': lambda v: 4.0 * math.exp(-2.0 * abs(v)) / (1.0 + math.exp(-2.0 * abs(v))) ** 2}   # csrc/hilo_ad.h::sech2_of
 
 
 class Dag:
@@ -235,6 +236,10 @@ class Dag:
             r = self.mul(self.recip(self.fun('sqrt', inner)), self.diff(a, wrt))
         elif op == 'atanh':
             r = self.mul(self.recip(self.sub(self.const(1.0), self.mul(a, a))), self.diff(a, wrt))
+        elif op == 'tanh':                                             # sech2 = 1 - tanh^2, native: no cancellation for large |a|
+            r = self.mul(self.fun('sech2', a), self.diff(a, wrt))
+        elif op == 'sech2':                                            # -2 tanh sech2 da
+            r = self.mul(self.mul(self.const(-2.0), self.mul(self.fun('tanh', a), i)), self.diff(a, wrt))
         elif op == 'atan2':                                            # (x dy - y dx) / (x^2 + y^2), node = atan2(a = y, b = x)
             num = self.sub(self.mul(b, self.diff(a, wrt)), self.mul(a, self.diff(b, wrt)))
             r = self.mul(num, self.recip(self.add(self.mul(a, a), self.mul(b, b))))

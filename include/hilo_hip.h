@@ -595,6 +595,23 @@ int hilo_nmpc_layout_capacity(int model_id, int taylor, int* n_cap, long long* l
    same lane values.  n in 1..8; ops[n] (host): 0 sum, 1 NaN-propagating maximum, 2 minimum, 3 plain maximum - only the mixes
    compiled in are accepted (HILO_EINVAL otherwise); in[64][n], out_new[n], out_plain[n] device memory */
 int hilo_ocp_reduce_selftest(int n, const int* ops, const double* in, double* out_new, double* out_plain, void* stream);
+/* developer aid: every operation of the derivative arithmetic (csrc/hilo_ad.h) at n points in each scalar type - double, FastD,
+   Dual<1>, Dual<12>, Jet2.  in[n][7] = operation (AD_* of csrc/hilo_ad_selftest.h), a, b, da, db, dda, ddb; out[n][20] in the layout
+   stated there; device memory */
+int hilo_ad_selftest(int64_t n, const double* in, double* out, void* stream);
+/* developer aid: the postfix interpreter (csrc/hilo_expr.h) on its own, for 4 states, 2 inputs and 3 parameters.  block (HOST,
+   block_len doubles): `count` programs back to back, validated like a solver's; program `which` is evaluated at n points in double
+   and in Jet2.  in[n][18] = x[4] dx[4] ddx[4] u[2] du[2] ddu[2], p[3], out[n][4] = value, then Jet2 v a b; device memory.
+   Returns after the launch has finished. */
+int hilo_expr_selftest(const double* block, int block_len, int count, int which, int64_t n, const double* in, const double* p,
+                       double* out, void* stream);
+/* developer aid: a model given as source (`struct UserModel`, the form the controllers and filters take) evaluated on its own at n
+   points, in a small run-time compiled unit apart from the filter unit: ode and meas in double, FastD, Dual<nx+nu> seeded with the
+   identity and Jet2 along a direction, and - where the source carries them - the generated jx / jh / mjh.  trig_calls != 0 compiles
+   sine and cosine behind calls (HILO_TRIG_CALLS, as the filter unit does).  Row layouts of in / out: csrc/hilo_jit.hip;
+   flags[2] (device): the source has symbolic derivatives, and their measurement part.  Returns after the launch has finished. */
+int hilo_jit_probe(const char* user_source, int trig_calls, int nx, int nu, int np, int ny, int64_t n, const double* in, double* out,
+                   int* flags, void* stream);
 /* x+ = Phi(x, u, p) with the controller's own shooting map: closed-loop harness (control_loop.py:343-396) */
 int hilo_nmpc_plant_step(hilo_nmpc* h, int64_t batch, const double* x, const double* u, const double* p,
                          int64_t p_stride, double* x_next, void* stream);

@@ -568,7 +568,8 @@ def eval_exprs(exprs, x, u, p, gps=()):
     val = {}
     fn = {'sin': math.sin, 'cos': math.cos, 'exp': math.exp, 'log': math.log, 'sqrt': math.sqrt, 'log10': math.log10,
           'fabs': math.fabs, 'sign': lambda v: float((v > 0) - (v < 0)), 'asin': math.asin, 'acos': math.acos, 'atan': math.atan,
-          'asinh': math.asinh, 'acosh': math.acosh, 'atanh': math.atanh}
+          'asinh': math.asinh, 'acosh': math.acosh, 'atanh': math.atanh, 'tanh': math.tanh,
+          'sech2': lambda v: 4.0 * math.exp(-2.0 * abs(v)) / (1.0 + math.exp(-2.0 * abs(v))) ** 2}
     for n in sorted(allnodes.values(), key=lambda q: q.serial):
         a = [val[id(c)] for c in n.args]
         op = n.op

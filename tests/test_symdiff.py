@@ -118,3 +118,46 @@ def test_the_reference_function_table_values_and_derivatives():
         Hn = np.array(Hs.subs({a: pt[0], b: pt[1], c: pt[2]}).evalf(20), dtype=float)
         got = g.evaluate(H, pt[:2], pt[2:], [], kb=kbv)
         np.testing.assert_allclose(got, [Hn[i][j] for i in range(3) for j in range(i + 1)], rtol=1e-11, atol=1e-13)
+
+
+def test_tanh_of_a_large_argument():
+    """tanh(1000 x), the smooth saturation term: composed of exp(2a) it was inf / inf beyond |a| = 354.9 (OverflowError in the host
+    evaluators, NaN on the device).  Values, the expression-level derivative and the symbolic DAG's first and contracted second
+    derivatives against mpmath at 50 digits, from a = 0 to |a| = 1000; where the exact derivative is below the smallest double the
+    result is exactly 0, elsewhere within 1e-13 relative (the tolerance the table test above applies to first derivatives, here
+    with the scale factor 1000 x of the argument's own rounding: d/da sech2 = -2 tanh sech2, one ulp of a = 400 moves it 2e-13)."""
+    import mpmath
+    import numpy as np
+    from hilo_mpc_amd import Model, expr
+    from hilo_mpc_amd.symdiff import derivative_dag
+    from tests.problems import eval_exprs
+    m = Model(name='sat')
+    x, u = m.set_dynamical_states(['a', 'b']), m.set_inputs(['c'])
+    m.set_dynamical_equations([expr.tanh(1000. * x[0]) * x[1], x[0] + u[0] * expr.tanh(x[1] * 1000.)])
+    m2 = Model(name='sat2')
+    m2.set_dynamical_states(['a', 'b']), m2.set_inputs(['c'])
+    m2.set_dynamical_equations(['tanh(1000. * a) * b', 'a + c * tanh(b * 1000.)'])
+    mp = mpmath.mp.clone()
+    mp.dps = 50
+    kbv = [.3, -1.7]
+    for pt in ((.4, -1., 1.3), (0., .02, -.6), (-1., 0., .8), (1e-4, -.3549, 2.), (.0051, 1., 1.)):
+        a, b, c = (mp.mpf(v) for v in pt)
+        ta, tb = mp.tanh(1000 * a), mp.tanh(1000 * b)
+        sa, sb = 1 / mp.cosh(1000 * a) ** 2, 1 / mp.cosh(1000 * b) ** 2
+        F = [ta * b, a + c * tb]
+        J = [[1000 * sa * b, ta, 0], [1, 1000 * c * sb, tb]]
+        H0 = [[-2e6 * ta * sa * b, 1000 * sa, 0], [1000 * sa, 0, 0], [0, 0, 0]]
+        H1 = [[0, 0, 0], [0, -2e6 * tb * sb * c, 1000 * sb], [0, 1000 * sb, 0]]
+        Hn = [[kbv[0] * H0[i][j] + kbv[1] * H1[i][j] for j in range(3)] for i in range(3)]
+        f64 = lambda M_: np.array([[float(v) for v in r] for r in M_])
+        for mod in (m, m2):
+            got = eval_exprs(mod._ode, pt[:2], pt[2:], [])
+            assert np.isfinite(got).all()
+            np.testing.assert_allclose(got, [float(v) for v in F], rtol=1e-14)
+            Je = expr.jacobian(mod._ode, list(mod.x) + list(mod.u))
+            np.testing.assert_allclose(eval_exprs([e for r in Je for e in r], pt[:2], pt[2:], []).reshape(2, 3), f64(J), rtol=1e-13, atol=0.)
+            g, fn, Jd, H, kb = derivative_dag(2, 1, mod._ode)
+            np.testing.assert_allclose(np.array(g.evaluate([Jd[i][j] for i in range(2) for j in range(3)], pt[:2], pt[2:], [])).reshape(2, 3),
+                                       f64(J), rtol=1e-13, atol=0.)
+            np.testing.assert_allclose(g.evaluate(H, pt[:2], pt[2:], [], kb=kbv), [f64(Hn)[i][j] for i in range(3) for j in range(i + 1)],
+                                       rtol=1e-12, atol=0.)
