@@ -108,6 +108,7 @@ def _declare(lib):
         'hilo_model_rollout': (C.c_int, [vp, P(SimOpts), i64, i32, vp, vp, i64, i64, vp, vp, vp, vp]),
         'hilo_model_rollout_resume': (C.c_int, [vp, P(SimOpts), i64, i32, vp, vp, i64, i64, vp, vp, vp, vp, vp]),
         'hilo_model_rollout_dae': (C.c_int, [vp, P(SimOpts), i64, i32, vp, vp, vp, i64, i64, vp, vp, vp, vp, vp]),
+        'hilo_model_rollout_sens': (C.c_int, [vp, P(SimOpts), i64, i32, vp, vp, i64, i64, i32, vp, vp, vp, vp, vp, vp]),
         'hilo_model_linearize': (C.c_int, [vp, i64, vp, vp, i64, vp, vp, vp, vp]),
         'hilo_lqr_gain': (C.c_int, [i32, i32, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, P(LqrOpts), vp, vp, vp, vp]),
         'hilo_lqr_call': (C.c_int, [vp, P(LqrOpts), i64, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]),

@@ -1310,4 +1310,308 @@ __device__ __forceinline__ void rollout_idas_body(const KP& kp, const SimParams&
     stats[b * 4 + 3] = c.n_rhs;
   }
 }
+
+// ---- forward sensitivities of the Dormand-Prince roll-out, one instance on a team of lanes -------------------------------------
+// `dopri5_sens_interval` integrates the augmented system
+//   dx/dt = f(t, x, u, p),   dS/dt = f_x S + f_theta,   theta = [x0; u; p],   S(0) = [I | 0 | 0]
+// with the pair, the controller and every convention of `dopri5_interval` above (stage times, first same as last, clipping at the
+// sampling instant, model_ode_at): what scipy's RK45 does when it is handed the vector [x; vec S].  The error norm and the norms
+// of the first-step estimate run over all NX (1 + NS) components, each with its own scale atol + rtol max(|.|, |.+|); n_rhs counts
+// one evaluation of the augmented right-hand side as one, so n_rhs == 6 (acc + rej) + 2 holds as before.
+//
+// Layout.  The NS selected columns of S are spread over a team of T lanes, T the smallest power of two >= NS (T <= 64).  A lane
+// carries the state x and NC columns as Dual<NC> numbers: the tangent of x is the column, the tangent of [u; p] is 1 at the
+// column's own entry and 0 elsewhere (the caller sets the seeds as DATA: no lane branches on its column), and one evaluation of
+// the functor on those duals is f next to f_x s + f_theta.  Every lane of a team carries x redundantly; a lane whose columns lie
+// behind NS carries zero columns, which stay zero and add nothing to a norm - the divisor is NX (1 + NS), not a count over lanes.
+// The device runs NC = 1 on the lane team; the host test (tests/test_sens_host.py) runs the same statements with every column in
+// one "lane" and a team of one.  NC > 1 on the device - fewer redundant copies of x for small models - is a tuning knob not used.
+//
+// Uniformity.  The value parts of x, of the slopes and of the trial point are computed from values alone - the same operations
+// on the same operands in every lane of a team - so the team's copies of x agree bit for bit as long as every lane takes the
+// same steps.  The ONE thing a step decides on that differs between lanes is the columns' share of the sum of squares, and it
+// enters every decision through `team.sum` only: the accept / reject test, the step-size factor, the loop exit, the step count,
+// max_steps and the too-small-step test read team-uniform values (a NaN in any lane's share makes the sum NaN in all of them: a
+// rejection for the team).  `LaneTeam::sum` is an xor butterfly: at each level a lane and its partner add the same two numbers,
+// and addition commutes, so after log2 T levels all T lanes hold the same bits - no broadcast.  Teams are aligned to T within the
+// wave, so the partner c ^ m, m < T, is a lane of the same team, which is in the loop whenever this lane is; the teams of a wave
+// run their own step sequences and no value crosses from one team to another.
+struct TeamOfOne {   // the host: every column in the one "lane"
+  HD double sum(double s) const { return s; }
+};
+struct LaneTeam {    // T lanes of a wave, aligned to T
+  int T;
+  __device__ __forceinline__ double sum(double s) const {
+    const int lane = (int)threadIdx.x;
+#pragma unroll 1
+    for (int m = 1; m < T; m <<= 1) {   // xor butterfly (see above)
+      const int src = (lane ^ m) << 2;
+      const int lo = __builtin_amdgcn_ds_bpermute(src, __double2loint(s));
+      const int hi = __builtin_amdgcn_ds_bpermute(src, __double2hiint(s));
+      s += __hiloint2double(hi, lo);
+    }
+    return s;
+  }
+};
+
+// Widest model the team kernel is built for.  A lane holds the ten vectors of a step (seven slopes, the state, the stage point and
+// the trial point) 2 NX doubles wide - value and tangent - next to the duals of [u; p] and the functor's temporaries, which are
+// twice as many as in doubles.  Measured like DOPRI5_MAX_NX, with a dense synthetic right-hand side (a sine, an exponential and two
+// products per state) on Dual<1>, cross-compiled for gfx950, registers of a lane's 512 / bytes of scratch per lane: 4 states 422 / 0,
+// 5 states 512 / 60, 6 states 512 / 284, 8 states 512 / 1092, 12 states 512 / 2872.  The zoo: Linear2 150, Bioreactor3 196,
+// Chemostat4 238, Pendulum4 260, no scratch.  A wider model is refused by the host (HILO_ENOTSUP) instead of being left to spill;
+// so is a run-time compiled one whose kernel reports scratch.
+constexpr int SENS_MAX_NX = 4;
+constexpr int SENS_X0 = 1, SENS_U = 2, SENS_P = 4;   // HILO_SENS_*: the groups of theta whose columns are carried, in this order
+
+template <int NX, int NC>
+struct SensCarry {   // Dopri5Carry with the slope at the current state as duals
+  Dual<NC> k1[NX];
+  double h, t, t0;
+  int status, n_acc, n_rej, n_rhs;
+  bool have_k1;
+};
+
+template <int NX, int NC>
+HD void sens_init(SensCarry<NX, NC>& c, double h0) {
+  c.h = h0 > 0.0 ? h0 : 0.0;
+  c.t = c.t0 = 0.0;
+  c.status = SIM_OK;
+  c.n_acc = c.n_rej = c.n_rhs = 0;
+  c.have_k1 = false;
+}
+
+// The seeds of the lane (or host "lane") whose first column is col0: x gets its values and the unit tangents of the x0 group,
+// [u; p] theirs.  Column j of the selection is entry j of [x0 | u | p] restricted to the groups of `wrt`; a column >= NS has no
+// entry anywhere and is a zero column.  Comparisons turned into 0.0 / 1.0: data, not branches.
+template <class M, int NC>
+HD void sens_seed_x(int wrt, int col0, const double* xv, Dual<NC>* x) {
+#pragma unroll
+  for (int i = 0; i < M::NX; ++i) {
+    x[i].v = xv[i];
+#pragma unroll
+    for (int q = 0; q < NC; ++q) x[i].d[q] = (double)((wrt & SENS_X0) != 0 && col0 + q == i);
+  }
+}
+template <class M, int NC>
+HD void sens_seed_up(int wrt, int col0, const double* upv, Dual<NC>* u, Dual<NC>* p) {
+  const int off_u = (wrt & SENS_X0) ? M::NX : 0, off_p = off_u + ((wrt & SENS_U) ? M::NU : 0);
+#pragma unroll
+  for (int i = 0; i < M::NU; ++i) {
+    u[i].v = upv[i];
+#pragma unroll
+    for (int q = 0; q < NC; ++q) u[i].d[q] = (double)((wrt & SENS_U) != 0 && col0 + q == off_u + i);
+  }
+#pragma unroll
+  for (int i = 0; i < M::NP; ++i) {
+    p[i].v = upv[M::NU + i];
+#pragma unroll
+    for (int q = 0; q < NC; ++q) p[i].d[q] = (double)((wrt & SENS_P) != 0 && col0 + q == off_p + i);
+  }
+}
+template <class M>
+HD int sens_columns(int wrt) {
+  return ((wrt & SENS_X0) ? M::NX : 0) + ((wrt & SENS_U) ? M::NU : 0) + ((wrt & SENS_P) ? M::NP : 0);
+}
+
+// sum over the augmented vector of (v / (atol + rtol max(|a|, |b|)))^2: the state's share (identical in every lane of a team,
+// counted once) plus the team's sum of the columns' shares
+template <int NX, int NC, class TEAM>
+HD double sens_sumsq(const TEAM& team, const Dual<NC>* v, const Dual<NC>* a, const Dual<NC>* b, double rtol, double atol) {
+  double sx = 0.0, sc = 0.0;
+#pragma unroll
+  for (int i = 0; i < NX; ++i) {
+    const double q = v[i].v / (atol + ::fmax(::fabs(a[i].v), ::fabs(b[i].v)) * rtol);
+    sx += q * q;
+#pragma unroll
+    for (int j = 0; j < NC; ++j) {
+      const double r = v[i].d[j] / (atol + ::fmax(::fabs(a[i].d[j]), ::fabs(b[i].d[j])) * rtol);
+      sc += r * r;
+    }
+  }
+  return sx + team.sum(sc);
+}
+
+// One sampling interval of the augmented system, in place in x (values and columns).  ns: the number of selected columns (the
+// norms' divisor is NX (1 + ns)); u, p: the inputs and parameters with their seeds.  Returns c.status, the same in every lane of a
+// team; on a failure x holds whatever the integration stopped at (the caller discards it).
+template <class M, int NC, class TEAM>
+HD int dopri5_sens_interval(SensCarry<M::NX, NC>& c, const TEAM& team, int ns, Dual<NC>* x, const Dual<NC>* u, const Dual<NC>* p,
+                            double dt, double rtol, double atol, int max_steps) {
+  constexpr int NX = M::NX;
+  using D = Dual<NC>;
+  constexpr double EPS = 2.220446049250313e-16;
+  constexpr double A21 = 1.0 / 5;
+  constexpr double A31 = 3.0 / 40, A32 = 9.0 / 40;
+  constexpr double A41 = 44.0 / 45, A42 = -56.0 / 15, A43 = 32.0 / 9;
+  constexpr double A51 = 19372.0 / 6561, A52 = -25360.0 / 2187, A53 = 64448.0 / 6561, A54 = -212.0 / 729;
+  constexpr double A61 = 9017.0 / 3168, A62 = -355.0 / 33, A63 = 46732.0 / 5247, A64 = 49.0 / 176, A65 = -5103.0 / 18656;
+  constexpr double B1 = 35.0 / 384, B3 = 500.0 / 1113, B4 = 125.0 / 192, B5 = -2187.0 / 6784, B6 = 11.0 / 84;
+  constexpr double E1 = -71.0 / 57600, E3 = 71.0 / 16695, E4 = -71.0 / 1920, E5 = 17253.0 / 339200, E6 = -22.0 / 525, E7 = 1.0 / 40;
+  constexpr bool TV = model_time_variant<M>::value;
+  constexpr double C2 = 1.0 / 5, C3 = 3.0 / 10, C4 = 4.0 / 5, C5 = 8.0 / 9;
+  const double n_aug = (double)(NX * (1 + ns));
+  double ts = 0.0;   // absolute time at the start of this interval (time-variant functors only)
+  if constexpr (TV) ts = c.t0 + c.t;
+  auto f = [&](double at_t, const D* at, D* k) {
+    model_ode_at<M>(at_t, at, u, p, dt, k);
+    ++c.n_rhs;
+  };
+  if (c.status != SIM_OK) return c.status;
+  if (!c.have_k1) {
+    f(ts, x, c.k1);
+    c.have_k1 = true;
+  }
+  if (!(c.h > 0.0)) {   // the first step of the roll-out: dopri5_interval's estimate over the augmented vector
+    D x1[NX], f1[NX];
+    const double d0 = ::sqrt(sens_sumsq<NX>(team, x, x, x, rtol, atol) / n_aug);
+    const double d1 = ::sqrt(sens_sumsq<NX>(team, c.k1, x, x, rtol, atol) / n_aug);
+    double h0 = (d0 < 1e-5 || d1 < 1e-5) ? 1e-6 : 0.01 * d0 / d1;
+    h0 = ::fmin(h0, dt);
+#pragma unroll
+    for (int i = 0; i < NX; ++i) x1[i] = x[i] + h0 * c.k1[i];
+    f(ts + h0, x1, f1);
+#pragma unroll
+    for (int i = 0; i < NX; ++i) f1[i] = f1[i] - c.k1[i];
+    const double d2 = ::sqrt(sens_sumsq<NX>(team, f1, x, x, rtol, atol) / n_aug) / h0;
+    const double h1 = (d1 <= 1e-15 && d2 <= 1e-15) ? ::fmax(1e-6, h0 * 1e-3) : ::pow(0.01 / ::fmax(d1, d2), 0.2);
+    c.h = ::fmin(::fmin(100.0 * h0, h1), dt);
+    if (!(c.h > 0.0)) c.h = dt;   // a non-finite estimate: the controller below finds the step (or fails)
+  }
+  double tl = 0.0;          // time inside this interval
+  bool rejected = false;    // the previous attempt of the CURRENT step was rejected
+  int attempts = 0;
+  while (tl < dt) {         // (tl, c.h, attempts: team-uniform)
+    if (attempts >= max_steps) return c.status = SIM_MAX_STEPS;
+    if constexpr (TV) {
+      if (c.h < 16.0 * EPS * ::fabs(ts + tl)) return c.status = SIM_STEP_TOO_SMALL;
+    } else {
+      if (c.h < 16.0 * EPS * ::fabs(c.t + tl)) return c.status = SIM_STEP_TOO_SMALL;
+    }
+    ++attempts;
+    const double rem = dt - tl;
+    const bool last = 1.01 * c.h >= rem;
+    const double h = last ? rem : c.h;
+    D k2[NX], k3[NX], k4[NX], k5[NX], k6[NX], k7[NX], xi[NX], xn[NX];
+    double tn = 0.0;   // absolute time at the start of this step
+    if constexpr (TV) tn = ts + tl;
+#pragma unroll
+    for (int i = 0; i < NX; ++i) xi[i] = x[i] + h * (A21 * c.k1[i]);
+    f(tn + C2 * h, xi, k2);
+#pragma unroll
+    for (int i = 0; i < NX; ++i) xi[i] = x[i] + h * (A31 * c.k1[i] + A32 * k2[i]);
+    f(tn + C3 * h, xi, k3);
+#pragma unroll
+    for (int i = 0; i < NX; ++i) xi[i] = x[i] + h * (A41 * c.k1[i] + A42 * k2[i] + A43 * k3[i]);
+    f(tn + C4 * h, xi, k4);
+#pragma unroll
+    for (int i = 0; i < NX; ++i) xi[i] = x[i] + h * (A51 * c.k1[i] + A52 * k2[i] + A53 * k3[i] + A54 * k4[i]);
+    f(tn + C5 * h, xi, k5);
+#pragma unroll
+    for (int i = 0; i < NX; ++i) xi[i] = x[i] + h * (A61 * c.k1[i] + A62 * k2[i] + A63 * k3[i] + A64 * k4[i] + A65 * k5[i]);
+    f(tn + h, xi, k6);
+#pragma unroll
+    for (int i = 0; i < NX; ++i) xn[i] = x[i] + h * (B1 * c.k1[i] + B3 * k3[i] + B4 * k4[i] + B5 * k5[i] + B6 * k6[i]);
+    f(last ? ts + dt : tn + h, xn, k7);
+#pragma unroll
+    for (int i = 0; i < NX; ++i) xi[i] = h * (E1 * c.k1[i] + E3 * k3[i] + E4 * k4[i] + E5 * k5[i] + E6 * k6[i] + E7 * k7[i]);   // (xi: the error estimate)
+    const double err = ::sqrt(sens_sumsq<NX>(team, xi, x, xn, rtol, atol) / n_aug);   // the step's one cross-lane value
+    if (err < 1.0) {   // accepted (a non-finite estimate fails this comparison: a rejection)
+      double fac = err == 0.0 ? 10.0 : ::fmin(10.0, 0.9 * ::pow(err, -0.2));
+      if (rejected) fac = ::fmin(1.0, fac);
+      c.h = last ? ::fmax(c.h, h * fac) : h * fac;
+      tl = last ? dt : tl + h;
+#pragma unroll
+      for (int i = 0; i < NX; ++i) { x[i] = xn[i]; c.k1[i] = k7[i]; }
+      ++c.n_acc;
+      rejected = false;
+    } else {
+      c.h = h * ::fmax(0.2, 0.9 * ::pow(err, -0.2));   // (NaN or inf: fmax answers 0.2)
+      ++c.n_rej;
+      rejected = true;
+    }
+  }
+  c.t += dt;
+  return c.status;
+}
+
+// The roll-out with sensitivities: 64 / T instances per wave, lane c of a team carries x and column c (NC = 1).  wrt: HILO_SENS_*
+// groups; T: the team size for sens_columns(wrt), chosen by the host.  X, Y, stats as in rollout_body, written by the team's first
+// lane (Y: the value part of the measurement on the duals);  SX [steps + 1][batch][NS][NX]: a lane writes its column as NX
+// contiguous doubles, row 0 the seed;  SY [steps][batch][NS][NY] = h_x S + h_theta at the end of each interval, or null.  An input
+// sequence (up_step != 0): the columns go on across the sampling instants with the new inputs' values (the host refuses SENS_U:
+// each interval's input would be a parameter of its own).  A failed instance gets NaN in SX / SY wherever it gets NaN in X.
+// A team whose instance lies behind the batch leaves as a whole, before the first exchange.
+template <class M, class KP>
+__device__ __forceinline__ void rollout_sens_body(const KP& kp, const SimParams& sp, int64_t batch, int steps,
+                                                  const double* __restrict__ x0, const double* __restrict__ up, int64_t up_stride,
+                                                  int64_t up_step, int wrt, int T, double* __restrict__ X, double* __restrict__ Y,
+                                                  double* __restrict__ SX, double* __restrict__ SY, int* __restrict__ stats,
+                                                  double t0) {
+  constexpr int NX = M::NX, NU = M::NU, NP = M::NP, NY = M::NY;
+  constexpr bool TV = model_time_variant<M>::value;
+  static_assert(!M::DISCRETE && NX <= SENS_MAX_NX, "the sensitivity roll-out integrates a continuous model of at most SENS_MAX_NX states");
+  const int lane = (int)threadIdx.x, col = lane & (T - 1);
+  const int64_t b = (int64_t)blockIdx.x * (ROLLOUT_TPB / T) + lane / T;
+  if (b >= batch) return;   // (b is the same in all T lanes of the team)
+  const int ns = sens_columns<M>(wrt);
+  const bool first = col == 0, mine = col < ns;
+  const LaneTeam team = {T};
+  Dual<1> x[NX], u[NU > 0 ? NU : 1], p[NP > 0 ? NP : 1];
+  double upv[NU + NP > 0 ? NU + NP : 1];
+  {
+    double xv[NX];
+#pragma unroll
+    for (int i = 0; i < NX; ++i) xv[i] = x0[b * NX + i];
+    sens_seed_x<M>(wrt, col, xv, x);
+  }
+#pragma unroll
+  for (int i = 0; i < NX; ++i) {
+    if (first) X[b * NX + i] = x[i].v;
+    if (mine) SX[(b * ns + col) * NX + i] = x[i].d[0];
+  }
+  SensCarry<NX, 1> c;
+  sens_init(c, sp.h0);
+  if constexpr (TV) c.t0 = t0;
+  const double nan = __builtin_nan("");
+  for (int k = 0; k < steps; ++k) {
+    double tk = 0.0;   // the start of this sampling interval
+    if constexpr (TV) {
+      c.t = k * kp.dt;
+      tk = t0 + c.t;
+    }
+    if (k == 0 || up_step != 0) {
+      const double* src = up + (int64_t)k * up_step + b * up_stride;
+#pragma unroll
+      for (int i = 0; i < NU + NP; ++i) upv[i] = src[i];
+      sens_seed_up<M>(wrt, col, upv, u, p);
+      c.have_k1 = false;   // the slope kept from the last step belongs to the previous interval's inputs
+    }
+    const bool ok = dopri5_sens_interval<M>(c, team, ns, x, u, p, kp.dt, sp.rtol, sp.atol, sp.max_steps) == SIM_OK;
+    const int64_t row = (int64_t)(k + 1) * batch + b;
+#pragma unroll
+    for (int i = 0; i < NX; ++i) {
+      if (first) X[row * NX + i] = ok ? x[i].v : nan;
+      if (mine) SX[(row * ns + col) * NX + i] = ok ? x[i].d[0] : nan;
+    }
+    if constexpr (NY > 0) {
+      if (Y != nullptr || SY != nullptr) {
+        Dual<1> yy[NY];
+        model_meas_at<M>(tk + kp.dt, x, u, p, kp.dt, yy);
+        const int64_t rowy = (int64_t)k * batch + b;
+#pragma unroll
+        for (int i = 0; i < NY; ++i) {
+          if (first && Y != nullptr) Y[rowy * NY + i] = ok ? yy[i].v : nan;
+          if (mine && SY != nullptr) SY[(rowy * ns + col) * NY + i] = ok ? yy[i].d[0] : nan;
+        }
+      }
+    }
+  }
+  if (stats != nullptr && first) {
+    stats[b * 4 + 0] = c.status;
+    stats[b * 4 + 1] = c.n_acc;
+    stats[b * 4 + 2] = c.n_rej;
+    stats[b * 4 + 3] = c.n_rhs;
+  }
+}
 }  // namespace hilo

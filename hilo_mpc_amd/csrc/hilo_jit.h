@@ -63,6 +63,8 @@ struct JitKfKernels {
   int rollout_bdf_scratch = 0;                   // bytes of scratch per lane of that kernel
   hipFunction_t rollout_idas = nullptr;          // a model with algebraic states in [x; z] (hilo_integrate.h::rollout_idas_body, SIM_IDAS);
   int rollout_idas_scratch = 0;                  // an empty kernel for every other model.  Bytes of scratch per lane of that kernel
+  hipFunction_t rollout_sens = nullptr;          // the explicit pair with forward sensitivities on a team of lanes
+  int rollout_sens_scratch = 0;                  // (hilo_integrate.h::rollout_sens_body).  Bytes of scratch per lane of that kernel
   int nz = 0;                                    // algebraic states of the functor (hilo_models.h::model_nz)
   hipFunction_t lqr_call = nullptr, lqr_linearize = nullptr;   // regulator gains and Jacobians of the model's map (hilo_lqr.h)
   int lqr_scratch = 0;                           // bytes of scratch per lane of the two (the larger)

@@ -460,6 +460,16 @@ extern "C" __global__ __launch_bounds__(ROLLOUT_TPB) void hilo_user_rollout_idas
     rollout_idas_body<UserModel>(kp, sp, batch, steps, x0, z0, up, up_stride, up_step, X, Z, Y, stats, (lds_double*)idas_lds);
   }
 }
+extern "C" __global__ __launch_bounds__(ROLLOUT_TPB) void hilo_user_rollout_sens(KfParams kp, SimParams sp, int64_t batch, int steps,
+                                                                                 const double* __restrict__ x0,
+                                                                                 const double* __restrict__ up, int64_t up_stride,
+                                                                                 int64_t up_step, int wrt, int T,
+                                                                                 double* __restrict__ X, double* __restrict__ Y,
+                                                                                 double* __restrict__ SX, double* __restrict__ SY,
+                                                                                 int* __restrict__ stats, double t0) {
+  if constexpr (!UserModel::DISCRETE && UserModel::NX <= SENS_MAX_NX && model_nz<UserModel>::value == 0)
+    rollout_sens_body<UserModel>(kp, sp, batch, steps, x0, up, up_stride, up_step, wrt, T, X, Y, SX, SY, stats, t0);
+}
 extern "C" __global__ __launch_bounds__(64) void hilo_user_lqr_call(KfParams kp, LqrParams o, int64_t batch, const double* __restrict__ x,
                                                                     const double* __restrict__ x_eq, const double* __restrict__ u_eq,
                                                                     const double* __restrict__ p, int64_t p_stride,
@@ -516,6 +526,8 @@ extern "C" __global__ void hilo_user_kf_info(int* o) {
   if (hipFuncGetAttribute(&k.rollout_bdf_scratch, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, k.rollout_bdf) != hipSuccess) k.rollout_bdf_scratch = 0;
   HILO_HIP_CHECK(hipModuleGetFunction(&k.rollout_idas, mod, "hilo_user_rollout_idas"));
   if (hipFuncGetAttribute(&k.rollout_idas_scratch, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, k.rollout_idas) != hipSuccess) k.rollout_idas_scratch = 0;
+  HILO_HIP_CHECK(hipModuleGetFunction(&k.rollout_sens, mod, "hilo_user_rollout_sens"));
+  if (hipFuncGetAttribute(&k.rollout_sens_scratch, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, k.rollout_sens) != hipSuccess) k.rollout_sens_scratch = 0;
   HILO_HIP_CHECK(hipModuleGetFunction(&k.lqr_call, mod, "hilo_user_lqr_call"));
   HILO_HIP_CHECK(hipModuleGetFunction(&k.lqr_linearize, mod, "hilo_user_lqr_linearize"));
   {

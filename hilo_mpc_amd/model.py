@@ -39,6 +39,7 @@ MODEL_USER = 100    # HILO_MODEL_USER: the model is defined by expressions and c
 # `solver_options` carries to `ca.integrator`), with CasADi's defaults for CVODES
 SOLVERS = {'dopri5': 1, 'bdf': 2, 'idas': 3}  # name -> hilo_sim_opts.method (HILO_SIM_DOPRI5, HILO_SIM_BDF, HILO_SIM_IDAS)
 IDAS_MAX_STATES = 8  # n_x + n_z of a model under 'idas' (HILO_SIM_BDF_MAX_NX: the store of the method in the LDS of one workgroup)
+SENS_MAX_NX = 4   # HILO_SIM_SENS_MAX_NX: the widest model the sensitivity roll-out is built for
 SOLVER_OPTIONS = {'reltol': 1e-6, 'abstol': 1e-8, 'max_num_steps': 10000, 'first_step': 0.}
 SIM_STATUS = {0: 'ok', 1: 'max_num_steps reached', 2: 'step size too small'}     # HILO_SIM_STATUS_*
 
@@ -812,14 +813,22 @@ class Model:
             self._plant = h
         return h
 
-    def step(self, x, u=None, p=None, device_index=None, t0=0.):
+    def step(self, x, u=None, p=None, device_index=None, t0=0., sensitivities=None):
         """x [B, n_x] -> (x_next [B, n_x], y [B, n_y]) after one sampling interval, on the device (numpy in -> numpy out).
-        t0: the time at which the interval starts, one value for the batch (read by a time-variant model only)."""
+        t0: the time at which the interval starts, one value for the batch (read by a time-variant model only).
+        sensitivities (under `setup(solver='dopri5')`; see `rollout`): a further output `sens` with the derivatives of x_next and y at
+        the end of the interval, `sens['x']['p']` [B, n_x, n_p] and so on - row 1 of the one-interval roll-out."""
         import torch
         from . import _lib
         from ._device import ptr, stream_ptr, to_dev
         if not self._is_setup:
             raise RuntimeError("Model is not set up. Run Model.setup() before running simulations.")
+        if sensitivities is not None:
+            xs, ys, sens = self.rollout(x, u, p, steps=1, device_index=device_index, t0=t0, sensitivities=sensitivities)
+            sens['x'] = {g: v[1] for g, v in sens['x'].items()}
+            if 'y' in sens:
+                sens['y'] = {g: v[0] for g, v in sens['y'].items()}
+            return xs[1], ys[0], sens
         if self._solver is not None or self.is_time_variant():   # one sampling interval under error control / with the time
             xs, ys = self.rollout(x, u, p, steps=1, device_index=device_index, t0=t0)
             return xs[1], ys[0]
@@ -849,7 +858,52 @@ class Model:
         xn, y = xn[:, 0], y[:, 0]
         return (xn.cpu().numpy(), y.cpu().numpy()) if host else (xn, y)
 
-    def rollout(self, x0, u=None, p=None, steps=1, return_stats=False, device_index=None, t0=0., _h=None, z0=None, return_z=False):
+    def _sensitivity_groups(self, sensitivities, n_p, is_sequence):
+        """The groups of `sensitivities=` in the order of the kernel's columns (x0, u, p) with their widths, after the refusals."""
+        have = {'x0': self.n_x, 'u': self.n_u, 'p': n_p}
+        if self._solver != 'dopri5':
+            if self._solver is None:
+                raise NotImplementedError("sensitivities are integrated next to the states by the explicit pair: the fixed-step maps "
+                                          "carry none. Set the model up with Model.setup(solver='dopri5') (a discrete or discretised "
+                                          "model: Model.linearization gives the Jacobians of its map)")
+            raise NotImplementedError(f"sensitivities under solver '{self._solver}' are not implemented (its difference tables leave no "
+                                      f"room for a second table per column). Use Model.setup(solver='dopri5'), or central differences "
+                                      f"through Model.rollout for a stiff model")
+        if sensitivities is True:
+            groups = tuple(g for g in ('x0', 'u', 'p') if have[g])
+        else:
+            if isinstance(sensitivities, str):
+                sensitivities = (sensitivities,)
+            groups = tuple(sensitivities)
+            for g in groups:
+                if g not in have:
+                    raise ValueError(f"sensitivities: unknown group '{g}'. Choose out of ('x0', 'u', 'p'), or pass True for every group "
+                                     f"the model has")
+                if not have[g]:
+                    raise ValueError(f"sensitivities: the model has no {'inputs' if g == 'u' else 'parameters'}, so there is no group "
+                                     f"'{g}'. Leave it out (True selects every group the model has)")
+            groups = tuple(g for g in ('x0', 'u', 'p') if g in groups)
+        if not groups:
+            raise ValueError("sensitivities: no group selected. Pass True or a tuple out of ('x0', 'u', 'p')")
+        if 'u' in groups and (is_sequence['inputs'] or is_sequence['parameters']):
+            raise ValueError("sensitivities: with an input sequence every sampling interval's input is a parameter of its own, so there "
+                             "is no one column per input. Select ('x0', 'p'), or hold the inputs (and parameters) over the roll-out "
+                             "(u [B, n_u])")
+        if 'p' in groups and is_sequence['parameters']:
+            raise ValueError("sensitivities: with a parameter sequence every sampling interval's parameters are parameters of their own. "
+                             "Select ('x0',), or hold the parameters over the roll-out (p [B, n_p])")
+        if self.n_x > SENS_MAX_NX:
+            raise NotImplementedError(f"sensitivities: the kernel keeps the pair's vectors twice as wide as the plain roll-out and is built "
+                                      f"for up to {SENS_MAX_NX} states; the model has {self.n_x}. Use central differences through "
+                                      f"Model.rollout")
+        ns = sum(have[g] for g in groups)
+        if ns > 64:
+            raise NotImplementedError(f"sensitivities: {ns} columns; an instance's columns are spread over the lanes of one wave, at "
+                                      f"most 64. Select fewer groups per call")
+        return [(g, have[g]) for g in groups]
+
+    def rollout(self, x0, u=None, p=None, steps=1, return_stats=False, device_index=None, t0=0., _h=None, z0=None, return_z=False,
+                sensitivities=None):
         """The many-interval sibling of `step`: `steps` sampling intervals for a batch of states in ONE launch
         (`hilo_model_rollout`), with the model's own map or, after `setup(solver='dopri5')` or `'bdf'`, under error control.
 
@@ -872,6 +926,21 @@ class Model:
         tau in [0, dt] - the inputs are held, time is not - and y[k] = h(t_k + dt, x[k + 1], u[k], p); a discrete model's map and
         measurement both see t_k: x[k + 1] = f(t_k, x[k], u[k], p), y[k] = h(t_k, x[k + 1], u[k], p).
 
+        sensitivities (under `setup(solver='dopri5')`): None - every return value as above; True - the forward sensitivities of the
+        trajectory with respect to every group the model has out of the initial state, the inputs and the parameters; a tuple out of
+        ('x0', 'u', 'p') - those groups.  The result gains a LAST element `sens = {'x': {...}, 'y': {...}}` with one entry per selected
+        group: `sens['x']['p']` [steps + 1, B, n_x, n_p] = dx[k] / dp (row 0 the seed: the identity for 'x0', zeros otherwise),
+        `sens['y']['p']` [steps, B, n_y, n_p] = h_x dx[k + 1]/dp + h_p, the others likewise ('y' only when the model has measurement
+        equations) - device tensors for device tensors, numpy otherwise; permuted views of the kernel's buffers [.., columns, n_x],
+        not copies.  The kernel (`hilo_model_rollout_sens`) integrates the augmented system dS/dt = f_x S + f_theta next to the state
+        with the same pair, the error norm over ALL components - what scipy's RK45 does on [x; vec S], what a CasADi integrator's
+        forward sensitivities are - so its step sequence, and x within the tolerance, differ from the roll-out without; one instance
+        runs on a team of lanes, one column per lane.  A failed instance gets NaN in sens wherever it gets NaN in x.  Refused: no
+        solver, 'bdf' or 'idas' (NotImplementedError); 'u' together with an input sequence and a group the model does not have
+        (ValueError); more than 4 states, more than 64 columns, a learned term, algebraic states.  Out of scope: sensitivities under
+        'bdf' / 'idas', of the fixed-step maps, in `simulate`, `Model.linearization` / `LQR` on continuous models, adjoint
+        (reverse) sensitivities.
+
         _h (what `simulate` keeps between its calls): a one-element list holding the 'dopri5' step-size proposals [B] that the previous
         roll-out ended with (None: none yet); they are this one's first steps and are replaced by the ones it ends with
         (`hilo_model_rollout_resume`)."""
@@ -893,7 +962,7 @@ class Model:
         host = not isinstance(x0, torch.Tensor)
         xt = to_dev(x0, dev).reshape(-1, self.n_x).contiguous()
         B = xt.shape[0]
-        parts = []
+        parts, is_sequence = [], {'inputs': False, 'parameters': False}
         for v, n, what in ((u, self.n_u, 'inputs'), (self.lti_parameters() if self.name == 'lti' else p, h._n_p, 'parameters')):
             if n:
                 if v is None:
@@ -907,6 +976,7 @@ class Model:
                 if t.shape[1] not in (1, B):
                     raise ValueError(f"{what}: batch {t.shape[1]} does not match {B} states")
                 parts.append(t)
+                is_sequence[what] = t.shape[0] > 1
         if len(parts) == 2:
             S, Bb = max(q.shape[0] for q in parts), max(q.shape[1] for q in parts)
             up = getattr(self, '_rollout_up', None)
@@ -923,6 +993,7 @@ class Model:
         X = torch.empty(steps + 1, B, self.n_x, dtype=torch.float64, device=dev)
         Y = torch.empty(steps, B, ny, dtype=torch.float64, device=dev)
         stats = torch.empty(B, 4, dtype=torch.int32, device=dev) if return_stats else None
+        sens_groups = None if sensitivities is None else self._sensitivity_groups(sensitivities, h._n_p, is_sequence)
         opts = _lib.SimOpts()
         opts.t0 = float(t0)
         if self._solver is not None:
@@ -939,6 +1010,13 @@ class Model:
             Z = torch.empty(steps + 1, B, self.n_z, dtype=torch.float64, device=dev) if return_z else None
             _lib.check(_lib.lib().hilo_model_rollout_dae(h._handle, ctypes.byref(opts), B, steps, ptr(xt), ptr(zt), ptr(up), up_stride,
                                                          up_step, ptr(X), ptr(Z), ptr(Y), ptr(stats), stream_ptr(dev)))
+        elif sens_groups is not None:
+            ns = sum(n for _, n in sens_groups)
+            wrt = sum({'x0': 1, 'u': 2, 'p': 4}[g] for g, _ in sens_groups)
+            SX = torch.empty(steps + 1, B, ns, self.n_x, dtype=torch.float64, device=dev)
+            SY = torch.empty(steps, B, ns, ny, dtype=torch.float64, device=dev) if ny else None
+            _lib.check(_lib.lib().hilo_model_rollout_sens(h._handle, ctypes.byref(opts), B, steps, ptr(xt), ptr(up), up_stride, up_step, wrt,
+                                                          ptr(X), ptr(Y), ptr(SX), ptr(SY), ptr(stats), stream_ptr(dev)))
         elif _h is not None and self._solver == 'dopri5':
             if _h[0] is None or _h[0].shape != (B,) or _h[0].device != xt.device:
                 _h[0] = torch.zeros(B, dtype=torch.float64, device=dev)
@@ -953,7 +1031,25 @@ class Model:
         if return_stats:
             st = stats.cpu().numpy() if host else stats
             out += ({'status': st[:, 0], 'n_accepted': st[:, 1], 'n_rejected': st[:, 2], 'n_rhs': st[:, 3]},)
+        if sens_groups is not None:
+            out += (self._sensitivity_views(sens_groups, SX.cpu().numpy() if host else SX,
+                                            None if SY is None else (SY.cpu().numpy() if host else SY)),)
         return out
+
+    @staticmethod
+    def _sensitivity_views(sens_groups, SX, SY):
+        """The kernel's buffers [rows, B, columns, n] cut into the groups' columns and turned to [rows, B, n, n_group]: views."""
+        def cut(S):
+            res, at = {}, 0
+            for g, n in sens_groups:
+                v = S[:, :, at:at + n]
+                res[g] = v.permute(0, 1, 3, 2) if hasattr(v, 'permute') else v.transpose(0, 1, 3, 2)
+                at += n
+            return res
+        sens = {'x': cut(SX)}
+        if SY is not None:
+            sens['y'] = cut(SY)
+        return sens
 
     def set_initial_conditions(self, x0, t0=0., z0=None):
         """dynamic_model.py:3360-3400 (a batch of states is allowed: [B, n_x])."""

@@ -248,6 +248,30 @@ int hilo_model_rollout_dae(hilo_kf* kf, const hilo_sim_opts* opts, int64_t batch
                            const double* z0 /* [batch][nz] or NULL */, const double* up, int64_t up_stride, int64_t up_step,
                            double* X, double* Z /* [steps+1][batch][nz] or NULL */, double* Y, int32_t* stats, void* stream);
 
+/* The HILO_SIM_DOPRI5 roll-out with FORWARD SENSITIVITIES: next to x the kernel integrates S = dx / d theta, theta = [x0; u; p]
+   restricted to the groups of `wrt` (HILO_SENS_X0 | HILO_SENS_U | HILO_SENS_P; columns in the order x0, u, p of the selected groups,
+   NS of them), as the augmented system dS/dt = f_x S + f_theta, S(0) = [I | 0 | 0], with the same pair and controller - what
+   scipy's RK45 does when handed [x; vec S], and what a CasADi integrator's forward sensitivities are in the reference.  The error
+   norm runs over all nx (1 + NS) components, each with its own scale atol + rtol max(|.|, |.+|), so the step sequence is NOT that of
+   hilo_model_rollout and X differs from its X within the tolerance; stats count one evaluation of the augmented right-hand side
+   as one (n_rhs == 6 (accepted + rejected) + 2).  One instance runs on a team of T lanes, T the smallest power of two >= NS
+   (csrc/hilo_integrate.h::rollout_sens_body); derivatives come from the model functor on dual numbers.
+     opts->method must be HILO_SIM_DOPRI5; the other fields, x0, up, up_stride, up_step, X, Y, stats as for hilo_model_rollout;
+     SX [steps+1][B][NS][nx]: column j of S at every sampling instant as nx contiguous doubles (row 0: the seed);
+     SY [steps][B][NS][ny] = h_x S + h_theta at the end of each interval, or NULL.
+   With an input sequence (up_step != 0) the columns of x0 and p go on across the sampling instants; HILO_SENS_U is refused there
+   (every interval's input would be a parameter of its own).  A failed instance gets NaN in SX / SY wherever it gets NaN in X.
+   HILO_ENOTSUP for another method, a discrete or discretised handle, a model with a learned term or with algebraic states, more than
+   HILO_SIM_SENS_MAX_NX states, NS > 64, HILO_SENS_U with an input sequence, and a run-time compiled model whose kernel needs scratch
+   memory; HILO_EINVAL for a `wrt` that selects no column. */
+#define HILO_SENS_X0 1
+#define HILO_SENS_U 2
+#define HILO_SENS_P 4
+#define HILO_SIM_SENS_MAX_NX 4
+int hilo_model_rollout_sens(hilo_kf* kf, const hilo_sim_opts* opts, int64_t batch, int steps, const double* x0, const double* up,
+                            int64_t up_stride, int64_t up_step, int32_t wrt, double* X, double* Y, double* SX, double* SY,
+                            int32_t* stats, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------- */
 /* Linear-quadratic regulator: batched linearisation, Riccati gains and feedback                            */
 /* replaces `LinearQuadraticRegulator.setup / call` (hilo_mpc/modules/controller/lqr.py:204-306)            */
