@@ -32,10 +32,11 @@ from .lmpc import LMPC
 from .control_loop import SimpleControlLoop
 from .pf import ParticleFilter
 from .lqr import LinearQuadraticRegulator, LQR
+from .pid import PID
 
 from .ann import ArtificialNeuralNetwork, ANN, Layer, Dense, Dropout
 
 PF = ParticleFilter
 
 __all__ += ['NMPC', 'SMPC', 'MovingHorizonEstimator', 'MHE', 'LMPC', 'expr', 'SimpleControlLoop', 'ParticleFilter', 'PF',
-            'LinearQuadraticRegulator', 'LQR', 'ArtificialNeuralNetwork', 'ANN', 'Layer', 'Dense', 'Dropout']
+            'LinearQuadraticRegulator', 'LQR', 'PID', 'ArtificialNeuralNetwork', 'ANN', 'Layer', 'Dense', 'Dropout']

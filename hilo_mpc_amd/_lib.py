@@ -35,6 +35,12 @@ class SimOpts(C.Structure):
                 ('t0', C.c_double)]
 
 
+class PidOpts(C.Structure):
+    """hilo_pid_opts: flags 1 = proportional on the process value, 2 = derivative on it, 4 = output limits."""
+    _fields_ = [('nsp', C.c_int32), ('flags', C.c_int32), ('pv_index', C.c_int32 * 4), ('pv_is_state', C.c_int32 * 4),
+                ('out_index', C.c_int32 * 4), ('lo', C.c_double * 4), ('hi', C.c_double * 4)]
+
+
 class LqrOpts(C.Structure):
     """hilo_lqr_opts: horizon 0 = stationary."""
     _fields_ = [('horizon', C.c_int32), ('max_iter', C.c_int32), ('tol', C.c_double)]
@@ -109,6 +115,9 @@ def _declare(lib):
         'hilo_model_rollout_resume': (C.c_int, [vp, P(SimOpts), i64, i32, vp, vp, i64, i64, vp, vp, vp, vp, vp]),
         'hilo_model_rollout_dae': (C.c_int, [vp, P(SimOpts), i64, i32, vp, vp, vp, i64, i64, vp, vp, vp, vp, vp]),
         'hilo_model_rollout_sens': (C.c_int, [vp, P(SimOpts), i64, i32, vp, vp, i64, i64, i32, vp, vp, vp, vp, vp, vp]),
+        'hilo_pid_call': (C.c_int, [P(PidOpts), i64, dbl, vp, vp, i64, vp, i64, vp, vp, vp]),
+        'hilo_pid_loop': (C.c_int, [vp, P(SimOpts), P(PidOpts), i64, i32, vp, vp, i64, vp, i64, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp,
+                                    vp, vp]),
         'hilo_model_linearize': (C.c_int, [vp, i64, vp, vp, i64, vp, vp, vp, vp]),
         'hilo_lqr_gain': (C.c_int, [i32, i32, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, P(LqrOpts), vp, vp, vp, vp]),
         'hilo_lqr_call': (C.c_int, [vp, P(LqrOpts), i64, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]),

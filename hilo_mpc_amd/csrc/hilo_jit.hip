@@ -357,7 +357,7 @@ int jit_nmpc_kernels(const JitRequest& r, int device, JitKernels* out) {
 }
 
 // ---- filters of models written as expressions: kf_body<UserModel, UKF, MODE> behind six extern "C" kernels, the fused / team /
-// particle variants, the roll-out (csrc/hilo_integrate.h::rollout_body) and the regulator (csrc/hilo_lqr.h) ----------------------
+// particle variants, the roll-out (csrc/hilo_integrate.h::rollout_body), the closed loop (csrc/hilo_pid.h) and the regulator (csrc/hilo_lqr.h) --
 static std::map<std::string, JitKfKernels> g_kf_loaded;
 
 int jit_kf_kernels(const std::string& user_source, int device, JitKfKernels* out, bool compile_only, bool private_module) {
@@ -372,7 +372,7 @@ int jit_kf_kernels(const std::string& user_source, int device, JitKfKernels* out
                   "unscented filter's prediction tiles, 64 x n_x (3 n_x + 2) doubles, pass the 160 KB of LDS at n_x = 10 - the model has %d",
                   KF_MAX_NX, nx);
   }
-  std::string tu = "#define HILO_TRIG_CALLS 1\n#include \"hilo_kf_kernel.h\"\n#include \"hilo_integrate.h\"\n#include \"hilo_lqr.h\"\nextern \"C\" { __device__ const double* hilo_user_gp[4]; }\nnamespace hilo {\n";
+  std::string tu = "#define HILO_TRIG_CALLS 1\n#include \"hilo_kf_kernel.h\"\n#include \"hilo_integrate.h\"\n#include \"hilo_pid.h\"\n#include \"hilo_lqr.h\"\nextern \"C\" { __device__ const double* hilo_user_gp[4]; }\nnamespace hilo {\n";
   tu += user_source;
   tu += R"(
 }  // namespace hilo
@@ -436,6 +436,20 @@ extern "C" __global__ __launch_bounds__(ROLLOUT_TPB) void hilo_user_rollout(KfPa
                                                                             double* __restrict__ Y, int* __restrict__ stats,
                                                                             double t0, double* __restrict__ hc) {
   rollout_body<UserModel>(kp, sp, batch, steps, x0, up, up_stride, up_step, X, Y, stats, nullptr, t0, hc);
+}
+extern "C" __global__ __launch_bounds__(ROLLOUT_TPB) void hilo_user_pid_loop(KfParams kp, SimParams sp, PidParams po, int64_t batch,
+                                                                             int steps, const double* __restrict__ x0,
+                                                                             const double* __restrict__ up, int64_t up_stride,
+                                                                             const double* __restrict__ spt, int64_t sp_stride,
+                                                                             int64_t sp_step, const double* __restrict__ gains,
+                                                                             int64_t gain_stride, double* __restrict__ mem,
+                                                                             double* __restrict__ X, double* __restrict__ U,
+                                                                             double* __restrict__ Y, double* __restrict__ J,
+                                                                             double* __restrict__ x_final, int* __restrict__ stats,
+                                                                             double t0, double* __restrict__ hc) {
+  if constexpr (UserModel::NU > 0 && model_nz<UserModel>::value == 0)
+    pid_loop_body<UserModel>(kp, sp, po, batch, steps, x0, up, up_stride, spt, sp_stride, sp_step, gains, gain_stride, mem, X, U, Y, J,
+                             x_final, stats, t0, hc);
 }
 extern "C" __global__ __launch_bounds__(ROLLOUT_TPB) void hilo_user_rollout_bdf(KfParams kp, SimParams sp, int64_t batch, int steps,
                                                                                 const double* __restrict__ x0,
@@ -522,6 +536,8 @@ extern "C" __global__ void hilo_user_kf_info(int* o) {
   HILO_HIP_CHECK(hipModuleGetFunction(&k.team[1], mod, "hilo_user_kf_ut"));
   HILO_HIP_CHECK(hipModuleGetFunction(&k.rollout, mod, "hilo_user_rollout"));
   if (hipFuncGetAttribute(&k.rollout_scratch, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, k.rollout) != hipSuccess) k.rollout_scratch = 0;
+  HILO_HIP_CHECK(hipModuleGetFunction(&k.pid_loop, mod, "hilo_user_pid_loop"));
+  if (hipFuncGetAttribute(&k.pid_loop_scratch, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, k.pid_loop) != hipSuccess) k.pid_loop_scratch = 0;
   HILO_HIP_CHECK(hipModuleGetFunction(&k.rollout_bdf, mod, "hilo_user_rollout_bdf"));
   if (hipFuncGetAttribute(&k.rollout_bdf_scratch, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, k.rollout_bdf) != hipSuccess) k.rollout_bdf_scratch = 0;
   HILO_HIP_CHECK(hipModuleGetFunction(&k.rollout_idas, mod, "hilo_user_rollout_idas"));

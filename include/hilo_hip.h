@@ -273,6 +273,55 @@ int hilo_model_rollout_sens(hilo_kf* kf, const hilo_sim_opts* opts, int64_t batc
                             int32_t* stats, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------- */
+/* PID: the batched law and closed loops of controller and plant in one launch                              */
+/* replaces `PID.setup / call` (hilo_mpc/modules/controller/pid.py:244-365)                                 */
+/* ------------------------------------------------------------------------------------------------------- */
+/* The velocity-form law per loop j (csrc/hilo_pid.h::pid_update): with e = sp - pv on three-sample windows,
+     delta = e[-1] - e[-2] (HILO_PID_P_ON_PV: -(pv[-1] - pv[-2])) + dt / t_i e[-1]
+             + t_d / dt (e[-1] - 2 e[-2] + e[-3]) (HILO_PID_D_ON_PV: -t_d / dt (pv[-1] - 2 pv[-2] + pv[-3]))
+     u = u_prev + k_p delta, with HILO_PID_LIMITS clamped to [lo[j], hi[j]]; the clamped value is the next u_prev (anti-windup)
+   A loop's memory is HILO_PID_MEM doubles - pv[-2], pv[-1], sp[-2], sp[-1], u_prev - all zero after a reset; the set-point history
+   starts at zero like the reference's, so the first call sees a set-point step.  nsp loops, at most HILO_PID_MAX_LOOPS.
+   pv_index / pv_is_state / out_index are read by hilo_pid_loop alone: loop j controls measurement number pv_index[j] of the
+   plant - or, with pv_is_state[j], state number pv_index[j] - through input number out_index[j]. */
+#define HILO_PID_MAX_LOOPS 4
+#define HILO_PID_MEM 5
+#define HILO_PID_P_ON_PV 1
+#define HILO_PID_D_ON_PV 2
+#define HILO_PID_LIMITS 4
+typedef struct hilo_pid_opts {
+  int32_t nsp;
+  int32_t flags;                              /* HILO_PID_* */
+  int32_t pv_index[HILO_PID_MAX_LOOPS];
+  int32_t pv_is_state[HILO_PID_MAX_LOOPS];
+  int32_t out_index[HILO_PID_MAX_LOOPS];
+  double lo[HILO_PID_MAX_LOOPS], hi[HILO_PID_MAX_LOOPS];   /* read with HILO_PID_LIMITS */
+} hilo_pid_opts;
+/* One call of the law for a batch (no handle; on the current device), one loop per lane: pv [B][nsp] (NULL: zeros); the set points
+   sp at sp + b sp_stride and the gains - rows k_p [nsp], t_i [nsp], t_d [nsp] - at gains + b gain_stride (a stride of 0: shared by
+   the batch); mem [B][nsp][HILO_PID_MEM] updated in place; u [B][nsp]. */
+int hilo_pid_call(const hilo_pid_opts* opts, int64_t batch, double dt, const double* pv, const double* sp, int64_t sp_stride,
+                  const double* gains, int64_t gain_stride, double* mem, double* u, void* stream);
+/* The closed loop in ONE launch, one instance per lane (csrc/hilo_pid.h::pid_loop_instance): per sampling interval k the process
+   values - the selected measurements h(t_k, x[k], u_applied, p) or states, u_applied the input vector of the previous interval (at
+   k = 0 the held inputs with the driven entries taken from the memory's u_prev) - the law with the set points of interval k at
+   sp + k sp_step + b sp_stride (either 0: held / shared), the driven entries of the input vector overwritten (the others keep the
+   held value of `up`, one row [u; p] per instance, up_stride 0: shared), and the plant advanced as hilo_model_rollout advances it.
+     sim     as for hilo_model_rollout; HILO_SIM_MAP and HILO_SIM_DOPRI5 alone (an input that jumps every interval would restart
+             the implicit methods every interval): HILO_ENOTSUP for the others
+     X [steps + 1][B][nx], U [steps][B][nsp] the controller outputs, Y [steps][B][ny] = h(x[k + 1], u[k], p): each may be NULL
+     J [B][nsp][4]   ISE = sum e_k^2 dt, IAE = sum |e_k| dt, ITAE = sum (k dt) |e_k| dt, TVU = sum |u_k - u_{k-1}|
+     x_final [B][nx], mem left where the loop ended, stats [B][4] or NULL as for hilo_model_rollout
+     h [B] or NULL: the step-size proposal of HILO_SIM_DOPRI5, taken over where positive and written back
+   An instance whose integration fails gets NaN rows from the instant it did not reach, NaN in J and x_final.  HILO_EINVAL for
+   nsp outside 1..min(nu, HILO_PID_MAX_LOOPS) and selectors out of range; HILO_ENOTSUP for a model with algebraic states and a
+   run-time compiled model whose kernel needs scratch memory under HILO_SIM_DOPRI5. */
+int hilo_pid_loop(hilo_kf* kf, const hilo_sim_opts* sim, const hilo_pid_opts* opts, int64_t batch, int steps, const double* x0,
+                  const double* up, int64_t up_stride, const double* sp, int64_t sp_stride, int64_t sp_step, const double* gains,
+                  int64_t gain_stride, double* mem, double* X, double* U, double* Y, double* J, double* x_final, int32_t* stats,
+                  double* h, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------- */
 /* Linear-quadratic regulator: batched linearisation, Riccati gains and feedback                            */
 /* replaces `LinearQuadraticRegulator.setup / call` (hilo_mpc/modules/controller/lqr.py:204-306)            */
 /* ------------------------------------------------------------------------------------------------------- */
