@@ -26,8 +26,14 @@
 //   measurement  a continuous model's y[k] = h(t_k + dt, x_{k+1}, u_k, p) (modules/base.py:1729)
 // The smallest admissible step is measured against the absolute time in either method.
 //
-// Everything up to `rollout_body` is `HD` and templated on the functor like erk_step / rk4_classic, for doubles only: the same
-// statements compile for the host (tests/test_integrate_host.py builds a driver around this header and runs it on the CPU).
+// One implementation per method.  `dopri5_core` is the pair for a value type and a norm policy: `dopri5_interval` is it on doubles,
+// `dopri5_sens_interval` on dual numbers over a team of lanes.  `ndf_interval` is the variable-order step loop for a system
+// policy: `bdf_interval` is it on dx/dt = f (OdeSystem), `idas_interval` on [x; z] (DaeSystem).  `select_initial_step` is the
+// first-step estimate of all four.  The roll-out bodies and the closed loop of hilo_pid.h share `rollout_load_up`,
+// `plant_interval` and `rollout_write_stats`.
+//
+// Everything up to `rollout_body` is `HD` and templated on the functor like erk_step / rk4_classic: the same statements compile
+// for the host (tests/test_integrate_host.py builds a driver around this header and runs it on the CPU).
 #pragma once
 #include "hilo_common.h"
 #include "hilo_models.h"
@@ -48,10 +54,11 @@ struct SimParams {   // mirrors hilo_sim_opts (include/hilo_hip.h) up to its sta
   double rtol, atol, h0;
 };
 
-// what one instance carries from one sampling interval to the next
-template <int NX>
+// what one instance carries from one sampling interval to the next.  T: the value type of the slope - double, or Dual<NC> for the
+// roll-out with sensitivities (SensCarry below)
+template <int NX, class T = double>
 struct Dopri5Carry {
-  double k1[NX];      // slope at the current state (valid when have_k1)
+  T k1[NX];           // slope at the current state (valid when have_k1)
   double h;           // step-size proposal (0: not chosen yet)
   double t;           // time since the start of the roll-out, at the start of the interval handed to dopri5_interval
   double t0;          // absolute time of the start of the roll-out (a time-variant functor is evaluated at t0 + t + ...)
@@ -59,8 +66,8 @@ struct Dopri5Carry {
   bool have_k1;
 };
 
-template <int NX>
-HD void dopri5_init(Dopri5Carry<NX>& c, double h0) {
+template <int NX, class T>
+HD void dopri5_init(Dopri5Carry<NX, T>& c, double h0) {
   c.h = h0 > 0.0 ? h0 : 0.0;
   c.t = c.t0 = 0.0;
   c.status = SIM_OK;
@@ -79,13 +86,66 @@ HD double dopri5_rms(const double* v, const double* scale) {
   return ::sqrt(s / NX);
 }
 
-// Integrates dx/dt = f(x, u, p) - or f(c.t0 + c.t + tau, x, u, p), tau in [0, dt], for a time-variant functor - over one sampling
-// interval of length dt, in place.  Returns c.status; on a failure x holds the
-// state at the time the integration stopped (the caller discards it).  `max_steps` bounds the attempted steps of this call (the
-// meaning of CasADi's `max_num_steps`: per integrator call).
-template <class M>
-HD int dopri5_interval(Dopri5Carry<M::NX>& c, double* x, const double* u, const double* p, double dt, double rtol, double atol,
-                       int max_steps) {
+// a vector whose entry i is formed where it is read (the error estimate of a step: kept as an array, the plain roll-out of a
+// time-variant model took two registers more and lost a wave per SIMD)
+template <class F>
+struct Lazy {
+  F f;
+  HD auto operator[](int i) const { return f(i); }
+};
+template <class F>
+HD Lazy<F> lazy(F f) { return {f}; }
+
+// The norm of the pair and of the first-step estimate as a policy: `sumsq(v, a, b)` is the sum over the vector of
+// (v / (atol + rtol max(|a|, |b|)))^2 - v an array or a Lazy - and `divisor()` the number of its components.  This one is the
+// plain vector of NX doubles; the one of the sensitivities (SensNorm below) adds the columns' share over a team of lanes.
+template <int NX>
+struct PlainNorm {
+  double rtol, atol;
+  template <class V>
+  HD double sumsq(const V& v, const double* a, const double* b) const {
+    double s = 0.0;
+#pragma unroll
+    for (int i = 0; i < NX; ++i) {
+      const double q = v[i] / (atol + ::fmax(::fabs(a[i]), ::fabs(b[i])) * rtol);
+      s += q * q;
+    }
+    return s;
+  }
+  HD double divisor() const { return NX; }
+};
+
+// scipy's select_initial_step (Hairer, Norsett, Wanner I, II.4) from the state x and the slope f0 there: the first step of a method
+// whose local error behaves like h^(1 / expo) - 0.2 for the pair, 0.5 for order 1 - at most `bound`.  `slope_at(h, x1, f1)`
+// evaluates the slope at the trial point x1 = x + h f0, h after the start, into f1 and answers whether it could (the trial point of
+// a model with algebraic states needs a Newton solve of its own); where it could not, the first guess stands.  A non-finite
+// estimate answers `bound`: the method's own step control then finds the step (or fails).
+template <int NX, class T, class NORM, class F>
+HD double select_initial_step(const NORM& norm, const T* x, const T* f0, double bound, double expo, F&& slope_at) {
+  const double n = norm.divisor();
+  const double d0 = ::sqrt(norm.sumsq(x, x, x) / n), d1 = ::sqrt(norm.sumsq(f0, x, x) / n);
+  double h0 = (d0 < 1e-5 || d1 < 1e-5) ? 1e-6 : 0.01 * d0 / d1;
+  h0 = ::fmin(h0, bound);
+  T x1[NX], f1[NX];
+#pragma unroll
+  for (int i = 0; i < NX; ++i) x1[i] = x[i] + h0 * f0[i];
+  double h = h0;
+  if (slope_at(h0, x1, f1)) {
+#pragma unroll
+    for (int i = 0; i < NX; ++i) f1[i] = f1[i] - f0[i];
+    const double d2 = ::sqrt(norm.sumsq(f1, x, x) / n) / h0;
+    const double h1 = (d1 <= 1e-15 && d2 <= 1e-15) ? ::fmax(1e-6, h0 * 1e-3) : ::pow(0.01 / ::fmax(d1, d2), expo);
+    h = ::fmin(::fmin(100.0 * h0, h1), bound);
+  }
+  return h > 0.0 ? h : bound;
+}
+
+// One sampling interval of length dt with the pair, in place in x, for the value type T (double, or Dual<NC>: the augmented system
+// of the sensitivities) under the norm `norm` - the one implementation behind dopri5_interval and dopri5_sens_interval.  Every
+// decision of a step (accept / reject, the factor, the loop exit, the two failures) reads `norm.sumsq` and values derived from it
+// alone.  u, p: of type UP (doubles, or duals that carry their seeds).
+template <class M, class T, class UP, class NORM>
+HD int dopri5_core(Dopri5Carry<M::NX, T>& c, const NORM& norm, T* x, const UP* u, const UP* p, double dt, int max_steps) {
   constexpr int NX = M::NX;
   constexpr double EPS = 2.220446049250313e-16;
   // Dormand & Prince (1980), the coefficients of RK5(4)7M
@@ -98,9 +158,10 @@ HD int dopri5_interval(Dopri5Carry<M::NX>& c, double* x, const double* u, const 
   constexpr double E1 = -71.0 / 57600, E3 = 71.0 / 16695, E4 = -71.0 / 1920, E5 = 17253.0 / 339200, E6 = -22.0 / 525, E7 = 1.0 / 40;
   constexpr bool TV = model_time_variant<M>::value;
   constexpr double C2 = 1.0 / 5, C3 = 3.0 / 10, C4 = 4.0 / 5, C5 = 8.0 / 9;
+  const double n = norm.divisor();
   double ts = 0.0;   // absolute time at the start of this interval (time-variant functors only)
   if constexpr (TV) ts = c.t0 + c.t;
-  auto f = [&](double at_t, const double* at, double* k) {
+  auto f = [&](double at_t, const T* at, T* k) {
     model_ode_at<M>(at_t, at, u, p, dt, k);
     ++c.n_rhs;
   };
@@ -109,23 +170,11 @@ HD int dopri5_interval(Dopri5Carry<M::NX>& c, double* x, const double* u, const 
     f(ts, x, c.k1);
     c.have_k1 = true;
   }
-  if (!(c.h > 0.0)) {   // the first step of the roll-out
-    double scale[NX], x1[NX], f1[NX];
-#pragma unroll
-    for (int i = 0; i < NX; ++i) scale[i] = atol + ::fabs(x[i]) * rtol;
-    const double d0 = dopri5_rms<NX>(x, scale), d1 = dopri5_rms<NX>(c.k1, scale);
-    double h0 = (d0 < 1e-5 || d1 < 1e-5) ? 1e-6 : 0.01 * d0 / d1;
-    h0 = ::fmin(h0, dt);
-#pragma unroll
-    for (int i = 0; i < NX; ++i) x1[i] = x[i] + h0 * c.k1[i];
-    f(ts + h0, x1, f1);
-#pragma unroll
-    for (int i = 0; i < NX; ++i) f1[i] -= c.k1[i];
-    const double d2 = dopri5_rms<NX>(f1, scale) / h0;
-    const double h1 = (d1 <= 1e-15 && d2 <= 1e-15) ? ::fmax(1e-6, h0 * 1e-3) : ::pow(0.01 / ::fmax(d1, d2), 0.2);
-    c.h = ::fmin(::fmin(100.0 * h0, h1), dt);
-    if (!(c.h > 0.0)) c.h = dt;   // a non-finite estimate: the controller below finds the step (or fails)
-  }
+  if (!(c.h > 0.0))   // the first step of the roll-out
+    c.h = select_initial_step<NX>(norm, x, c.k1, dt, 0.2, [&](double h0, const T* x1, T* f1) {
+      f(ts + h0, x1, f1);
+      return true;
+    });
   double tl = 0.0;          // time inside this interval
   bool rejected = false;    // the previous attempt of the CURRENT step was rejected
   int attempts = 0;
@@ -141,7 +190,7 @@ HD int dopri5_interval(Dopri5Carry<M::NX>& c, double* x, const double* u, const 
     const double rem = dt - tl;
     const bool last = 1.01 * c.h >= rem;
     const double h = last ? rem : c.h;
-    double k2[NX], k3[NX], k4[NX], k5[NX], k6[NX], k7[NX], xi[NX], xn[NX];
+    T k2[NX], k3[NX], k4[NX], k5[NX], k6[NX], k7[NX], xi[NX], xn[NX];
     double tn = 0.0;   // absolute time at the start of this step
     if constexpr (TV) tn = ts + tl;
 #pragma unroll
@@ -162,14 +211,8 @@ HD int dopri5_interval(Dopri5Carry<M::NX>& c, double* x, const double* u, const 
 #pragma unroll
     for (int i = 0; i < NX; ++i) xn[i] = x[i] + h * (B1 * c.k1[i] + B3 * k3[i] + B4 * k4[i] + B5 * k5[i] + B6 * k6[i]);
     f(last ? ts + dt : tn + h, xn, k7);
-    double s = 0.0;
-#pragma unroll
-    for (int i = 0; i < NX; ++i) {
-      const double e = h * (E1 * c.k1[i] + E3 * k3[i] + E4 * k4[i] + E5 * k5[i] + E6 * k6[i] + E7 * k7[i]);
-      const double q = e / (atol + ::fmax(::fabs(x[i]), ::fabs(xn[i])) * rtol);
-      s += q * q;
-    }
-    const double err = ::sqrt(s / NX);
+    const auto e = lazy([&](int i) { return h * (E1 * c.k1[i] + E3 * k3[i] + E4 * k4[i] + E5 * k5[i] + E6 * k6[i] + E7 * k7[i]); });
+    const double err = ::sqrt(norm.sumsq(e, x, xn) / n);   // the step's one value that may cross lanes
     if (err < 1.0) {   // accepted (a non-finite estimate fails this comparison: a rejection)
       double fac = err == 0.0 ? 10.0 : ::fmin(10.0, 0.9 * ::pow(err, -0.2));
       if (rejected) fac = ::fmin(1.0, fac);
@@ -190,9 +233,19 @@ HD int dopri5_interval(Dopri5Carry<M::NX>& c, double* x, const double* u, const 
   return c.status;
 }
 
+// Integrates dx/dt = f(x, u, p) - or f(c.t0 + c.t + tau, x, u, p), tau in [0, dt], for a time-variant functor - over one sampling
+// interval of length dt, in place.  Returns c.status; on a failure x holds the state at the time the integration stopped (the
+// caller discards it).  `max_steps` bounds the attempted steps of this call (the meaning of CasADi's `max_num_steps`: per
+// integrator call).
+template <class M>
+HD int dopri5_interval(Dopri5Carry<M::NX>& c, double* x, const double* u, const double* p, double dt, double rtol, double atol,
+                       int max_steps) {
+  return dopri5_core<M>(c, PlainNorm<M::NX>{rtol, atol}, x, u, p, dt, max_steps);
+}
+
 // ---- variable-order implicit integration ----------------------------------------------------------------------------------
-// `bdf_interval` is the variable-order (1..5) backward differentiation method of scipy's `BDF` (scipy/integrate/_ivp/bdf.py,
-// common.py::select_initial_step), restated statement by statement - the NDF constants, the table of backward differences D with
+// `ndf_interval` - `bdf_interval` is it on dx/dt = f - is the variable-order (1..5) backward differentiation method of scipy's `BDF`
+// (scipy/integrate/_ivp/bdf.py, common.py::select_initial_step), restated statement by statement - the NDF constants, the table of backward differences D with
 // MAX_ORDER + 3 rows and its rescaling `change_D`, the simplified Newton iteration, the retry logic (a stale Jacobian is renewed
 // before the step is halved; I - c J is factorised again whenever c = h / alpha[order] changes), the error estimate, the count of
 // equal steps and the order selection - so that its step sequence can be compared with a solver everybody has.  What differs:
@@ -408,59 +461,44 @@ HD void bdf_solve(const MEM& mem, double* b) {
   }
 }
 
-// Advances dx/dt = f(x, u, p) - or f(c.t0 + t, x, u, p) for a time-variant functor - until the integration time reaches t_target (<= c.t_bound) and reads the state at t_target off the
-// interpolant of the difference table (scipy's BdfDenseOutput) into x.  A step may pass t_target - and later targets, which the
-// next calls then only interpolate; the end of the integration alone clips a step.  On the first call after bdf_init /
-// bdf_restart x is the initial state.  Returns c.status; on a failure x is left as it was (the caller discards it).  `max_steps`
-// bounds the attempted steps of this call, h0 > 0 is the first step.
-template <class M, class MEM>
-HD int bdf_interval(BdfCarry<M::NX>& c, const MEM& mem, double* x, const double* u, const double* p, double dt, double t_target,
-                    double rtol, double atol, double h0, int max_steps) {
-  constexpr int NX = M::NX;
+// the end of a start (bdf_start, idas_start): the difference table of order 1 from the state y and its slope yp, c.h chosen
+template <int N, class MEM>
+HD void ndf_begin(BdfCarry<N>& c, const MEM& mem, const double* y, const double* yp) {
+  for (int r = 0; r < BDF_MAX_ORDER + 3; ++r)
+#pragma unroll
+    for (int i = 0; i < N; ++i) mem.D(r, i) = r == 0 ? y[i] : (r == 1 ? yp[i] * c.h : 0.0);
+  c.t = 0.0;
+  c.order = 1;
+  c.n_equal = 0;
+  c.have_lu = false;
+  c.started = true;
+}
+
+// The variable-order step loop, once, for a system policy SYS - OdeSystem below, DaeSystem in the next section - that supplies
+// what differs between dx/dt = f and the DAE in [x; z]:
+//   N, ND        the length of the vector and the number of its differential rows (residual c f - psi - d; the others: -f)
+//   TV, time     whether the equations name the time, and the absolute time of the integration's t handed to rhs and jacobian
+//   rhs, jacobian, factor, change_D   the right-hand side F(t, y), dF/dy into the store, the factors of the Newton matrix for
+//                c = h / alpha[order], the rescaling of the difference table
+//   start        the set-up of an integration on the first call after bdf_init / bdf_restart
+//   finish       from the interpolated vector at t_target to the value handed out; false: SIM_IC_FAILED
+// Advances until the integration time reaches t_target (<= c.t_bound) and reads the vector at t_target off the interpolant of the
+// difference table (scipy's BdfDenseOutput) into y.  A step may pass t_target - and later targets, which the next calls then only
+// interpolate; the end of the integration alone clips a step.  Returns c.status; on a failure y is left as it was (the caller
+// discards it).  `max_steps` bounds the attempted steps of this call, h0 > 0 is the first step.
+template <class SYS, class MEM>
+HD int ndf_interval(const SYS& sys, BdfCarry<SYS::N>& c, const MEM& mem, double* y_out, double t_target, double rtol, double atol,
+                    double h0, int max_steps) {
+  constexpr int N = SYS::N, ND = SYS::ND;
   constexpr double EPS = 2.220446049250313e-16;
-  constexpr bool TV = model_time_variant<M>::value;
   if (c.status != SIM_OK) return c.status;
-  if (!c.started) {
-    double f0[NX];
-    model_ode_at<M>(c.t0, x, u, p, dt, f0);
-    ++c.n_rhs;
-    bdf_jacobian<M>(mem, x, u, p, dt, c.t0);
-    ++c.n_jac;
-    if (h0 > 0.0) {
-      c.h = ::fmin(h0, c.t_bound);
-    } else {   // select_initial_step with order = 1
-      double scale[NX], x1[NX], f1[NX];
-#pragma unroll
-      for (int i = 0; i < NX; ++i) scale[i] = atol + ::fabs(x[i]) * rtol;
-      const double d0 = dopri5_rms<NX>(x, scale), d1 = dopri5_rms<NX>(f0, scale);
-      double hh = (d0 < 1e-5 || d1 < 1e-5) ? 1e-6 : 0.01 * d0 / d1;
-      hh = ::fmin(hh, c.t_bound);
-#pragma unroll
-      for (int i = 0; i < NX; ++i) x1[i] = x[i] + hh * f0[i];
-      model_ode_at<M>(c.t0 + hh, x1, u, p, dt, f1);
-      ++c.n_rhs;
-#pragma unroll
-      for (int i = 0; i < NX; ++i) f1[i] -= f0[i];
-      const double d2 = dopri5_rms<NX>(f1, scale) / hh;
-      const double h1 = (d1 <= 1e-15 && d2 <= 1e-15) ? ::fmax(1e-6, hh * 1e-3) : ::pow(0.01 / ::fmax(d1, d2), 0.5);
-      c.h = ::fmin(::fmin(100.0 * hh, h1), c.t_bound);
-      if (!(c.h > 0.0)) c.h = c.t_bound;   // a non-finite estimate: the Newton iteration below fails and finds the step (or gives up)
-    }
-    for (int r = 0; r < BDF_MAX_ORDER + 3; ++r)
-#pragma unroll
-      for (int i = 0; i < NX; ++i) mem.D(r, i) = r == 0 ? x[i] : (r == 1 ? f0[i] * c.h : 0.0);
-    c.t = 0.0;
-    c.order = 1;
-    c.n_equal = 0;
-    c.have_lu = false;
-    c.started = true;
-  }
+  if (!c.started && sys.start(c, mem, y_out, rtol, atol, h0) != SIM_OK) return c.status;
   const double newton_tol = ::fmax(10.0 * EPS / rtol, ::fmin(0.03, ::sqrt(rtol)));
   int attempts = 0;
   while (c.t < t_target) {   // one pass: scipy's _step_impl
     double min_step;
-    if constexpr (TV) {
-      const double ta = c.t0 + c.t;
+    if constexpr (SYS::TV) {
+      const double ta = sys.time(c, c.t);
       min_step = 10.0 * ::fabs(::nextafter(ta, INFINITY) - ta);
     } else {
       min_step = 10.0 * (::nextafter(c.t, INFINITY) - c.t);
@@ -468,13 +506,13 @@ HD int bdf_interval(BdfCarry<M::NX>& c, const MEM& mem, double* x, const double*
     double h = c.h;
     int order = c.order;
     if (h < min_step) {
-      bdf_change_D<NX>(mem, order, min_step / h);
+      sys.change_D(mem, order, min_step / h);
       h = min_step;
       c.n_equal = 0;
     }
     bool current_jac = false, accepted = false;
     double t_new = c.t, safety = 0.0, error_norm = 0.0;
-    double scale[NX], d[NX];
+    double scale[N], d[N];
     while (!accepted) {
       if (attempts >= max_steps) return c.status = SIM_MAX_STEPS;
       if (!(h >= min_step)) return c.status = SIM_STEP_TOO_SMALL;
@@ -482,21 +520,21 @@ HD int bdf_interval(BdfCarry<M::NX>& c, const MEM& mem, double* x, const double*
       t_new = c.t + h;
       if (t_new > c.t_bound) {
         t_new = c.t_bound;
-        bdf_change_D<NX>(mem, order, (t_new - c.t) / h);
+        sys.change_D(mem, order, (t_new - c.t) / h);
         c.n_equal = 0;
         c.have_lu = false;
       }
       h = t_new - c.t;
-      double y_predict[NX], psi[NX], y[NX];
+      double y_predict[N], psi[N], y[N];
 #pragma unroll
-      for (int i = 0; i < NX; ++i) {
+      for (int i = 0; i < N; ++i) {
         y_predict[i] = mem.D(0, i);
         psi[i] = 0.0;
       }
       for (int j = 1; j <= order; ++j) {
         const double g = bdf_gamma(j);
 #pragma unroll
-        for (int i = 0; i < NX; ++i) {
+        for (int i = 0; i < N; ++i) {
           const double v = mem.D(j, i);
           y_predict[i] += v;
           psi[i] += v * g;
@@ -504,7 +542,7 @@ HD int bdf_interval(BdfCarry<M::NX>& c, const MEM& mem, double* x, const double*
       }
       const double alpha = bdf_alpha(order);
 #pragma unroll
-      for (int i = 0; i < NX; ++i) {
+      for (int i = 0; i < N; ++i) {
         scale[i] = atol + rtol * ::fabs(y_predict[i]);
         psi[i] /= alpha;
       }
@@ -513,36 +551,36 @@ HD int bdf_interval(BdfCarry<M::NX>& c, const MEM& mem, double* x, const double*
       int n_iter = 0;
       while (!converged) {
         if (!c.have_lu) {
-          c.have_lu = bdf_factor<NX>(mem, cc);
+          c.have_lu = sys.factor(mem, cc);
           ++c.n_lu;
         }
         if (c.have_lu) {   // solve_bdf_system
           double dy_norm_old = -1.0;   // (none yet)
 #pragma unroll
-          for (int i = 0; i < NX; ++i) {
+          for (int i = 0; i < N; ++i) {
             d[i] = 0.0;
             y[i] = y_predict[i];
           }
 #pragma unroll 1
           for (int k = 0; k < BDF_NEWTON_MAXITER; ++k) {
             n_iter = k + 1;
-            double f[NX];
-            model_ode_at<M>(c.t0 + t_new, y, u, p, dt, f);
+            double f[N];
+            sys.rhs(sys.time(c, t_new), y, f);
             ++c.n_rhs;
             bool finite = true;
 #pragma unroll
-            for (int i = 0; i < NX; ++i) finite = finite && ::fabs(f[i]) < INFINITY;
+            for (int i = 0; i < N; ++i) finite = finite && ::fabs(f[i]) < INFINITY;
             if (!finite) break;
 #pragma unroll
-            for (int i = 0; i < NX; ++i) f[i] = cc * f[i] - psi[i] - d[i];
-            bdf_solve<NX>(mem, f);   // f: dy
-            const double dy_norm = dopri5_rms<NX>(f, scale);
+            for (int i = 0; i < N; ++i) f[i] = i < ND ? cc * f[i] - psi[i] - d[i] : -f[i];
+            bdf_solve<N>(mem, f);   // f: dy
+            const double dy_norm = dopri5_rms<N>(f, scale);
             if (!(dy_norm < INFINITY)) break;
             const bool have_rate = dy_norm_old >= 0.0;
             const double rate = dy_norm / dy_norm_old;
             if (have_rate && !(rate < 1.0 && ::pow(rate, (double)(BDF_NEWTON_MAXITER - k)) / (1.0 - rate) * dy_norm <= newton_tol)) break;
 #pragma unroll
-            for (int i = 0; i < NX; ++i) {
+            for (int i = 0; i < N; ++i) {
               y[i] += f[i];
               d[i] += f[i];
             }
@@ -555,7 +593,7 @@ HD int bdf_interval(BdfCarry<M::NX>& c, const MEM& mem, double* x, const double*
         }
         if (!converged) {
           if (current_jac) break;
-          bdf_jacobian<M>(mem, y_predict, u, p, dt, c.t0 + t_new);
+          sys.jacobian(mem, sys.time(c, t_new), y_predict);
           ++c.n_jac;
           c.have_lu = false;
           current_jac = true;
@@ -563,7 +601,7 @@ HD int bdf_interval(BdfCarry<M::NX>& c, const MEM& mem, double* x, const double*
       }
       if (!converged) {
         h *= 0.5;
-        bdf_change_D<NX>(mem, order, 0.5);
+        sys.change_D(mem, order, 0.5);
         c.n_equal = 0;
         c.have_lu = false;
         ++c.n_rej;
@@ -573,16 +611,16 @@ HD int bdf_interval(BdfCarry<M::NX>& c, const MEM& mem, double* x, const double*
       const double ec = bdf_error_const(order);
       double s = 0.0;
 #pragma unroll
-      for (int i = 0; i < NX; ++i) {
+      for (int i = 0; i < N; ++i) {
         scale[i] = atol + rtol * ::fabs(y[i]);
         const double q = ec * d[i] / scale[i];
         s += q * q;
       }
-      error_norm = ::sqrt(s / NX);
+      error_norm = ::sqrt(s / N);
       if (!(error_norm <= 1.0)) {   // (a non-finite estimate fails the comparison: a rejection)
         const double factor = ::fmax(BDF_MIN_FACTOR, safety * ::pow(error_norm, -1.0 / (order + 1)));
         h *= factor;
-        bdf_change_D<NX>(mem, order, factor);
+        sys.change_D(mem, order, factor);
         c.n_equal = 0;   // the factors stay: the iteration had no trouble converging
         ++c.n_rej;
       } else {
@@ -595,26 +633,26 @@ HD int bdf_interval(BdfCarry<M::NX>& c, const MEM& mem, double* x, const double*
     c.h = h;
     // D^{j+1} y_n = D^j y_n - D^j y_{n-1}, d = D^{order+1} y_n
 #pragma unroll
-    for (int i = 0; i < NX; ++i) {
+    for (int i = 0; i < N; ++i) {
       mem.D(order + 2, i) = d[i] - mem.D(order + 1, i);
       mem.D(order + 1, i) = d[i];
     }
     for (int j = order; j >= 0; --j)
 #pragma unroll
-      for (int i = 0; i < NX; ++i) mem.D(j, i) += mem.D(j + 1, i);
+      for (int i = 0; i < N; ++i) mem.D(j, i) += mem.D(j + 1, i);
     if (c.n_equal < order + 1) continue;
     double sm = 0.0, sp = 0.0;
     {
       const double em = bdf_error_const(order - 1), ep = bdf_error_const(order + 1);
 #pragma unroll
-      for (int i = 0; i < NX; ++i) {
+      for (int i = 0; i < N; ++i) {
         const double qm = em * mem.D(order, i) / scale[i], qp = ep * mem.D(order + 2, i) / scale[i];
         sm += qm * qm;
         sp += qp * qp;
       }
     }
-    const double error_m_norm = order > 1 ? ::sqrt(sm / NX) : INFINITY;
-    const double error_p_norm = order < BDF_MAX_ORDER ? ::sqrt(sp / NX) : INFINITY;
+    const double error_m_norm = order > 1 ? ::sqrt(sm / N) : INFINITY;
+    const double error_p_norm = order < BDF_MAX_ORDER ? ::sqrt(sp / N) : INFINITY;
     const double fm = ::pow(error_m_norm, -1.0 / order), f0 = ::pow(error_norm, -1.0 / (order + 1)),
                  fp = ::pow(error_p_norm, -1.0 / (order + 2));
     double fmax_ = fm;   // argmax: the first of equal ones
@@ -626,29 +664,87 @@ HD int bdf_interval(BdfCarry<M::NX>& c, const MEM& mem, double* x, const double*
     c.order = order;
     const double factor = ::fmin(BDF_MAX_FACTOR, safety * fmax_);
     c.h *= factor;
-    bdf_change_D<NX>(mem, order, factor);
+    sys.change_D(mem, order, factor);
     c.n_equal = 0;
     c.have_lu = false;
   }
   // BdfDenseOutput at t_target
-  double acc[NX];
+  double acc[N];
 #pragma unroll
-  for (int i = 0; i < NX; ++i) acc[i] = 0.0;
+  for (int i = 0; i < N; ++i) acc[i] = 0.0;
   double prod = 1.0;
   for (int j = 0; j < c.order; ++j) {
     prod *= (t_target - (c.t - c.h * j)) / (c.h * (1 + j));
 #pragma unroll
-    for (int i = 0; i < NX; ++i) acc[i] += mem.D(j + 1, i) * prod;
+    for (int i = 0; i < N; ++i) acc[i] += mem.D(j + 1, i) * prod;
   }
 #pragma unroll
-  for (int i = 0; i < NX; ++i) x[i] = acc[i] + mem.D(0, i);
+  for (int i = 0; i < N; ++i) acc[i] += mem.D(0, i);
+  if (!sys.finish(acc)) return c.status = SIM_IC_FAILED;
+#pragma unroll
+  for (int i = 0; i < N; ++i) y_out[i] = acc[i];
   return c.status;
 }
 
+// The start of an integration of dx/dt = f from x: the slope and the Jacobian there, the first step (h0 > 0, or
+// select_initial_step with order = 1) and the difference table.  Called by bdf_interval on the first call after bdf_init /
+// bdf_restart.  Returns c.status.
+template <class M, class MEM>
+HD int bdf_start(BdfCarry<M::NX>& c, const MEM& mem, const double* x, const double* u, const double* p, double dt, double rtol,
+                 double atol, double h0) {
+  constexpr int NX = M::NX;
+  if (c.status != SIM_OK || c.started) return c.status;
+  double f0[NX];
+  model_ode_at<M>(c.t0, x, u, p, dt, f0);
+  ++c.n_rhs;
+  bdf_jacobian<M>(mem, x, u, p, dt, c.t0);
+  ++c.n_jac;
+  if (h0 > 0.0)
+    c.h = ::fmin(h0, c.t_bound);
+  else   // (a non-finite estimate answers t_bound: the Newton iteration of the step fails and finds the step, or gives up)
+    c.h = select_initial_step<NX>(PlainNorm<NX>{rtol, atol}, x, f0, c.t_bound, 0.5, [&](double hh, const double* x1, double* f1) {
+      model_ode_at<M>(c.t0 + hh, x1, u, p, dt, f1);
+      ++c.n_rhs;
+      return true;
+    });
+  ndf_begin(c, mem, x, f0);
+  return c.status;
+}
+
+// dx/dt = f(x, u, p) - or f(c.t0 + t, x, u, p) for a time-variant functor - as a system of ndf_interval
+template <class M>
+struct OdeSystem {
+  static constexpr int N = M::NX, ND = M::NX;   // every row is differential: the residual's selection folds at compile time
+  static constexpr bool TV = model_time_variant<M>::value;
+  const double *u, *p;
+  double dt;
+  HD double time(const BdfCarry<N>& c, double t) const { return c.t0 + t; }   // (read by a time-variant functor only)
+  HD void rhs(double t, const double* y, double* f) const { model_ode_at<M>(t, y, u, p, dt, f); }
+  template <class MEM>
+  HD void jacobian(const MEM& mem, double t, const double* y) const { bdf_jacobian<M>(mem, y, u, p, dt, t); }
+  template <class MEM>
+  HD bool factor(const MEM& mem, double cc) const { return bdf_factor<N>(mem, cc); }
+  // deliberately inlined at its five sites, where DaeSystem calls one function: the kernels of this path are the ones they were
+  template <class MEM>
+  HD void change_D(const MEM& mem, int order, double factor) const { bdf_change_D<N>(mem, order, factor); }
+  template <class MEM>
+  HD int start(BdfCarry<N>& c, const MEM& mem, const double* x, double rtol, double atol, double h0) const {
+    return bdf_start<M>(c, mem, x, u, p, dt, rtol, atol, h0);
+  }
+  HD bool finish(double*) const { return true; }   // the interpolated state is the answer
+};
+
+// ndf_interval on dx/dt = f: on the first call after bdf_init / bdf_restart x is the initial state, afterwards the state at t_target.
+template <class M, class MEM>
+HD int bdf_interval(BdfCarry<M::NX>& c, const MEM& mem, double* x, const double* u, const double* p, double dt, double t_target,
+                    double rtol, double atol, double h0, int max_steps) {
+  return ndf_interval(OdeSystem<M>{u, p, dt}, c, mem, x, t_target, rtol, atol, h0, max_steps);
+}
+
 // ---- variable-order implicit integration of a model with algebraic states ---------------------------------------------------
-// `idas_interval` is `bdf_interval` on the semi-explicit index-1 DAE  dx/dt = f(x, z, u, p),  0 = g(x, z, u, p)  IN THE COMBINED
+// `idas_interval` is `ndf_interval` on the semi-explicit index-1 DAE  dx/dt = f(x, z, u, p),  0 = g(x, z, u, p)  IN THE COMBINED
 // VECTOR w = [x; z] (N = NX + NZ entries), where the reference integrates such a model with IDAS: the NDF constants, the difference
-// table, change_D, the retry logic, the order selection and the dense output are the statements above with N in place of NX, on
+// table, change_D, the retry logic, the order selection and the dense output are the one step loop above under DaeSystem, on
 // the same store (BdfMem<N>, bdf_entries(N) doubles per instance).  With the mass matrix M = diag(I_NX, 0) and c = h / alpha[order]
 // the corrector solves M (psi + d) = c F(w_predict + d), F = [f; g]; the algebraic rows are divided by c.  What differs:
 //   Newton system   rows (I - c f_x, -c f_z) with residual c f - psi_x - d_x, rows (g_x, g_z) with residual -g: a small step leaves
@@ -835,38 +931,21 @@ HD int idas_start(BdfCarry<M::NX + M::NZ>& c, const MEM& mem, double* w, const d
     for (int i = 0; i < N; ++i) ok = ok && ::fabs(wp[i]) < INFINITY;
     if (!ok) return c.status = SIM_IC_FAILED;
   }
-  if (h0 > 0.0) {
+  if (h0 > 0.0)
     c.h = ::fmin(h0, c.t_bound);
-  } else {   // select_initial_step with order = 1 on dx/dt = f(x, zeta(x))
-    double scale[NX], w1[N], f1[N];
+  else   // select_initial_step with order = 1 on dx/dt = f(x, zeta(x)): the norms run over the differential states
+    c.h = select_initial_step<NX>(PlainNorm<NX>{rtol, atol}, w, wp, c.t_bound, 0.5, [&](double, const double* x1, double* f1) {
+      double w1[N], F1[N];
 #pragma unroll
-    for (int i = 0; i < NX; ++i) scale[i] = atol + ::fabs(w[i]) * rtol;
-    const double d0 = dopri5_rms<NX>(w, scale), d1 = dopri5_rms<NX>(wp, scale);
-    double hh = (d0 < 1e-5 || d1 < 1e-5) ? 1e-6 : 0.01 * d0 / d1;
-    hh = ::fmin(hh, c.t_bound);
-#pragma unroll
-    for (int i = 0; i < N; ++i) w1[i] = i < NX ? w[i] + hh * wp[i] : w[i];
-    if (idas_newton_z<M>(w1, w1 + NX, u, p)) {
-      idas_rhs<M>(w1, u, p, f1);
+      for (int i = 0; i < N; ++i) w1[i] = i < NX ? x1[i] : w[i];
+      if (!idas_newton_z<M>(w1, w1 + NX, u, p)) return false;   // the algebraic equations have no root at the trial point
+      idas_rhs<M>(w1, u, p, F1);
       ++c.n_rhs;
 #pragma unroll
-      for (int i = 0; i < NX; ++i) f1[i] -= wp[i];
-      const double d2 = dopri5_rms<NX>(f1, scale) / hh;
-      const double h1 = (d1 <= 1e-15 && d2 <= 1e-15) ? ::fmax(1e-6, hh * 1e-3) : ::pow(0.01 / ::fmax(d1, d2), 0.5);
-      c.h = ::fmin(::fmin(100.0 * hh, h1), c.t_bound);
-    } else {
-      c.h = hh;   // the algebraic equations have no root at the trial point: the first guess stands
-    }
-    if (!(c.h > 0.0)) c.h = c.t_bound;   // a non-finite estimate: the Newton iteration of the step fails and finds the step (or gives up)
-  }
-  for (int r = 0; r < BDF_MAX_ORDER + 3; ++r)
-#pragma unroll
-    for (int i = 0; i < N; ++i) mem.D(r, i) = r == 0 ? w[i] : (r == 1 ? wp[i] * c.h : 0.0);
-  c.t = 0.0;
-  c.order = 1;
-  c.n_equal = 0;
-  c.have_lu = false;
-  c.started = true;
+      for (int i = 0; i < NX; ++i) f1[i] = F1[i];
+      return true;
+    });
+  ndf_begin(c, mem, w, wp);
   return c.status;
 }
 
@@ -877,207 +956,84 @@ __host__ __device__ __attribute__((noinline)) void idas_change_D(MEM mem, int or
   bdf_change_D<N>(mem, order, factor);
 }
 
-// Advances the DAE until the integration time reaches t_target (<= c.t_bound) and reads w = [x; z] at t_target off the interpolant,
-// z corrected onto g(x, z) = 0.  On the first call after bdf_init / bdf_restart w holds the initial x and the start of the Newton
-// iteration for z.  Returns c.status; on a failure w is left as it was (the caller discards it).  The correction of z at t_target is
-// held to the exit test of the consistent start: where its sweeps do not bring the residual to round-off - a badly scaled g, a
-// singular dg/dz on the way - the instance ends with SIM_IC_FAILED at THAT instant, whichever it is.  The other arguments:
-// bdf_interval's.
+// the DAE in w = [x; z] as a system of ndf_interval (autonomous: a time-variant DAE is not built)
+template <class M>
+struct DaeSystem {
+  static constexpr int NX = M::NX, NZ = M::NZ, N = NX + NZ, ND = NX;
+  static constexpr bool TV = false;
+  const double *u, *p;
+  HD double time(const BdfCarry<N>&, double t) const { return t; }   // (not read)
+  HD void rhs(double, const double* w, double* F) const { idas_rhs<M>(w, u, p, F); }   // one pair; n_rhs counts pairs
+  template <class MEM>
+  HD void jacobian(const MEM& mem, double, const double* w) const { idas_jacobian<M>(mem, w, u, p); }
+  template <class MEM>
+  HD bool factor(const MEM& mem, double cc) const { return idas_factor<NX, NZ>(mem, cc); }
+  // deliberately ONE non-inlined function for the five sites, where OdeSystem inlines: see idas_change_D
+  template <class MEM>
+  HD void change_D(const MEM& mem, int order, double factor) const { idas_change_D<N>(mem, order, factor); }
+  template <class MEM>
+  HD int start(BdfCarry<N>& c, const MEM& mem, double* w, double rtol, double atol, double h0) const {
+    return idas_start<M>(c, mem, w, u, p, rtol, atol, h0);
+  }
+  // z of the interpolated pair onto g(x, z) = 0 (sweeps not counted in n_rhs; the integrator's own state is not touched)
+  HD bool finish(double* w) const { return idas_newton_z<M>(w, w + NX, u, p); }
+};
+
+// ndf_interval on the DAE: advances until the integration time reaches t_target (<= c.t_bound) and reads w = [x; z] at t_target off
+// the interpolant, z corrected onto g(x, z) = 0.  On the first call after bdf_init / bdf_restart w holds the initial x and the
+// start of the Newton iteration for z.  Returns c.status; on a failure w is left as it was (the caller discards it).  The correction
+// of z at t_target is held to the exit test of the consistent start: where its sweeps do not bring the residual to round-off - a
+// badly scaled g, a singular dg/dz on the way - the instance ends with SIM_IC_FAILED at THAT instant, whichever it is.  The other
+// arguments: bdf_interval's.
 template <class M, class MEM>
 HD int idas_interval(BdfCarry<M::NX + M::NZ>& c, const MEM& mem, double* w, const double* u, const double* p, double t_target,
                      double rtol, double atol, double h0, int max_steps) {
-  constexpr int NX = M::NX, NZ = M::NZ, N = NX + NZ;
-  constexpr double EPS = 2.220446049250313e-16;
-  if (c.status != SIM_OK) return c.status;
-  if (!c.started && idas_start<M>(c, mem, w, u, p, rtol, atol, h0) != SIM_OK) return c.status;
-  const double newton_tol = ::fmax(10.0 * EPS / rtol, ::fmin(0.03, ::sqrt(rtol)));
-  int attempts = 0;
-  while (c.t < t_target) {   // one pass: scipy's _step_impl
-    const double min_step = 10.0 * (::nextafter(c.t, INFINITY) - c.t);
-    double h = c.h;
-    int order = c.order;
-    if (h < min_step) {
-      idas_change_D<N>(mem, order, min_step / h);
-      h = min_step;
-      c.n_equal = 0;
-    }
-    bool current_jac = false, accepted = false;
-    double t_new = c.t, safety = 0.0, error_norm = 0.0;
-    double scale[N], d[N];
-    while (!accepted) {
-      if (attempts >= max_steps) return c.status = SIM_MAX_STEPS;
-      if (!(h >= min_step)) return c.status = SIM_STEP_TOO_SMALL;
-      ++attempts;
-      t_new = c.t + h;
-      if (t_new > c.t_bound) {
-        t_new = c.t_bound;
-        idas_change_D<N>(mem, order, (t_new - c.t) / h);
-        c.n_equal = 0;
-        c.have_lu = false;
-      }
-      h = t_new - c.t;
-      double y_predict[N], psi[N], y[N];
-#pragma unroll
-      for (int i = 0; i < N; ++i) {
-        y_predict[i] = mem.D(0, i);
-        psi[i] = 0.0;
-      }
-      for (int j = 1; j <= order; ++j) {
-        const double g = bdf_gamma(j);
-#pragma unroll
-        for (int i = 0; i < N; ++i) {
-          const double v = mem.D(j, i);
-          y_predict[i] += v;
-          psi[i] += v * g;
-        }
-      }
-      const double alpha = bdf_alpha(order);
-#pragma unroll
-      for (int i = 0; i < N; ++i) {
-        scale[i] = atol + rtol * ::fabs(y_predict[i]);
-        psi[i] /= alpha;
-      }
-      const double cc = h / alpha;
-      bool converged = false;
-      int n_iter = 0;
-      while (!converged) {
-        if (!c.have_lu) {
-          c.have_lu = idas_factor<NX, NZ>(mem, cc);
-          ++c.n_lu;
-        }
-        if (c.have_lu) {   // solve_bdf_system
-          double dy_norm_old = -1.0;   // (none yet)
-#pragma unroll
-          for (int i = 0; i < N; ++i) {
-            d[i] = 0.0;
-            y[i] = y_predict[i];
-          }
-#pragma unroll 1
-          for (int k = 0; k < BDF_NEWTON_MAXITER; ++k) {
-            n_iter = k + 1;
-            double f[N];
-            idas_rhs<M>(y, u, p, f);
-            ++c.n_rhs;
-            bool finite = true;
-#pragma unroll
-            for (int i = 0; i < N; ++i) finite = finite && ::fabs(f[i]) < INFINITY;
-            if (!finite) break;
-#pragma unroll
-            for (int i = 0; i < N; ++i) f[i] = i < NX ? cc * f[i] - psi[i] - d[i] : -f[i];
-            bdf_solve<N>(mem, f);   // f: dy
-            const double dy_norm = dopri5_rms<N>(f, scale);
-            if (!(dy_norm < INFINITY)) break;
-            const bool have_rate = dy_norm_old >= 0.0;
-            const double rate = dy_norm / dy_norm_old;
-            if (have_rate && !(rate < 1.0 && ::pow(rate, (double)(BDF_NEWTON_MAXITER - k)) / (1.0 - rate) * dy_norm <= newton_tol)) break;
-#pragma unroll
-            for (int i = 0; i < N; ++i) {
-              y[i] += f[i];
-              d[i] += f[i];
-            }
-            if (dy_norm == 0.0 || (have_rate && rate / (1.0 - rate) * dy_norm < newton_tol)) {
-              converged = true;
-              break;
-            }
-            dy_norm_old = dy_norm;
-          }
-        }
-        if (!converged) {
-          if (current_jac) break;
-          idas_jacobian<M>(mem, y_predict, u, p);
-          ++c.n_jac;
-          c.have_lu = false;
-          current_jac = true;
-        }
-      }
-      if (!converged) {
-        h *= 0.5;
-        idas_change_D<N>(mem, order, 0.5);
-        c.n_equal = 0;
-        c.have_lu = false;
-        ++c.n_rej;
-        continue;
-      }
-      safety = 0.9 * (2 * BDF_NEWTON_MAXITER + 1) / (2 * BDF_NEWTON_MAXITER + n_iter);
-      const double ec = bdf_error_const(order);
-      double s = 0.0;
-#pragma unroll
-      for (int i = 0; i < N; ++i) {
-        scale[i] = atol + rtol * ::fabs(y[i]);
-        const double q = ec * d[i] / scale[i];
-        s += q * q;
-      }
-      error_norm = ::sqrt(s / N);
-      if (!(error_norm <= 1.0)) {   // (a non-finite estimate fails the comparison: a rejection)
-        const double factor = ::fmax(BDF_MIN_FACTOR, safety * ::pow(error_norm, -1.0 / (order + 1)));
-        h *= factor;
-        idas_change_D<N>(mem, order, factor);
-        c.n_equal = 0;   // the factors stay: the iteration had no trouble converging
-        ++c.n_rej;
-      } else {
-        accepted = true;
-      }
-    }
-    ++c.n_equal;
-    ++c.n_acc;
-    c.t = t_new;
-    c.h = h;
-    // D^{j+1} y_n = D^j y_n - D^j y_{n-1}, d = D^{order+1} y_n
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-      mem.D(order + 2, i) = d[i] - mem.D(order + 1, i);
-      mem.D(order + 1, i) = d[i];
-    }
-    for (int j = order; j >= 0; --j)
-#pragma unroll
-      for (int i = 0; i < N; ++i) mem.D(j, i) += mem.D(j + 1, i);
-    if (c.n_equal < order + 1) continue;
-    double sm = 0.0, sp = 0.0;
-    {
-      const double em = bdf_error_const(order - 1), ep = bdf_error_const(order + 1);
-#pragma unroll
-      for (int i = 0; i < N; ++i) {
-        const double qm = em * mem.D(order, i) / scale[i], qp = ep * mem.D(order + 2, i) / scale[i];
-        sm += qm * qm;
-        sp += qp * qp;
-      }
-    }
-    const double error_m_norm = order > 1 ? ::sqrt(sm / N) : INFINITY;
-    const double error_p_norm = order < BDF_MAX_ORDER ? ::sqrt(sp / N) : INFINITY;
-    const double fm = ::pow(error_m_norm, -1.0 / order), f0 = ::pow(error_norm, -1.0 / (order + 1)),
-                 fp = ::pow(error_p_norm, -1.0 / (order + 2));
-    double fmax_ = fm;   // argmax: the first of equal ones
-    int delta = -1;
-    if (f0 > fmax_) { fmax_ = f0; delta = 0; }
-    if (fp > fmax_) { fmax_ = fp; delta = 1; }
-    if (order + delta < 1) delta = 0;   // (order 1: fm is 0 and can only win against two zeros)
-    order += delta;
-    c.order = order;
-    const double factor = ::fmin(BDF_MAX_FACTOR, safety * fmax_);
-    c.h *= factor;
-    idas_change_D<N>(mem, order, factor);
-    c.n_equal = 0;
-    c.have_lu = false;
-  }
-  // BdfDenseOutput at t_target, then z onto g(x, z) = 0
-  double acc[N];
-#pragma unroll
-  for (int i = 0; i < N; ++i) acc[i] = 0.0;
-  double prod = 1.0;
-  for (int j = 0; j < c.order; ++j) {
-    prod *= (t_target - (c.t - c.h * j)) / (c.h * (1 + j));
-#pragma unroll
-    for (int i = 0; i < N; ++i) acc[i] += mem.D(j + 1, i) * prod;
-  }
-#pragma unroll
-  for (int i = 0; i < N; ++i) acc[i] += mem.D(0, i);
-  if (!idas_newton_z<M>(acc, acc + NX, u, p)) return c.status = SIM_IC_FAILED;
-#pragma unroll
-  for (int i = 0; i < N; ++i) w[i] = acc[i];
-  return c.status;
+  return ndf_interval(DaeSystem<M>{u, p}, c, mem, w, t_target, rtol, atol, h0, max_steps);
 }
 
 constexpr int ROLLOUT_TPB = 64;   // one wave per workgroup: a slow instance holds back 63 others, not 255
+
+// ---- what the roll-out bodies below and the closed loop (hilo_pid.h::pid_loop_instance) share ---------------------------------
+// the row [u; p] of interval k and instance b into upv (strides: see rollout_body)
+template <class M>
+HD void rollout_load_up(const double* __restrict__ up, int64_t up_step, int64_t up_stride, int k, int64_t b, double* upv) {
+  const double* src = up + (int64_t)k * up_step + b * up_stride;
+#pragma unroll
+  for (int i = 0; i < M::NU + M::NP; ++i) upv[i] = src[i];
+}
+
+// stats [batch][4] (or null) of instance b from its carry
+template <class C>
+HD void rollout_write_stats(int* __restrict__ stats, int64_t b, const C& c) {
+  if (stats == nullptr) return;
+  stats[b * 4 + 0] = c.status;
+  stats[b * 4 + 1] = c.n_acc;
+  stats[b * 4 + 2] = c.n_rej;
+  stats[b * 4 + 3] = c.n_rhs;
+}
+
+// The plant over one sampling interval that starts at tk, in place in x: the handle's map or the pair, chosen by METHOD (SIM_MAP /
+// SIM_DOPRI5 builds that path alone, -1 chooses by sp.method at run time).  The pair is built for continuous models up to
+// DOPRI5_MAX_NX states - the host refuses the others - and carries its state in PlantCarry.  False: the integration failed.
+template <class M>
+constexpr bool plant_adaptive = !M::DISCRETE && M::NX <= DOPRI5_MAX_NX;
+template <class M>
+using PlantCarry = Dopri5Carry<plant_adaptive<M> ? M::NX : 1>;
+template <class M, int METHOD, class KP>
+HD bool plant_interval(const KP& kp, const SimParams& sp, PlantCarry<M>& c, double* x, const double* u, const double* p, double tk) {
+  constexpr int NX = M::NX;
+  bool ok = true;
+  if (METHOD == SIM_DOPRI5 || (METHOD < 0 && sp.method == SIM_DOPRI5)) {
+    if constexpr (plant_adaptive<M> && METHOD != SIM_MAP) ok = dopri5_interval<M>(c, x, u, p, kp.dt, sp.rtol, sp.atol, sp.max_steps) == SIM_OK;
+  } else if constexpr (METHOD != SIM_DOPRI5) {
+    double xo[NX];
+    if (kp.continuous && !M::DISCRETE) model_step<M>(4, kp.n_sub, x, u, p, kp.dt, xo, NoExt(), tk);
+    else model_step<M>(kp.erk_order, kp.n_sub, x, u, p, kp.dt, xo, NoExt(), tk);
+#pragma unroll
+    for (int i = 0; i < NX; ++i) x[i] = xo[i];
+  }
+  return ok;
+}
 
 // One instance per lane.  X [steps + 1][batch][NX] (row 0: x0), Y [steps][batch][NY] or null, stats [batch][4] (status, accepted,
 // rejected, right-hand-side evaluations) or null; up: rows [u; p] of instance b at up + k up_step + b up_stride (up_step 0: held
@@ -1120,8 +1076,8 @@ __device__ __forceinline__ void rollout_body(const KP& kp, const SimParams& sp, 
     x[i] = x0[b * NX + i];
     X[b * NX + i] = x[i];
   }
-  constexpr bool ADAPTIVE = !M::DISCRETE && NX <= DOPRI5_MAX_NX;
-  Dopri5Carry<ADAPTIVE ? NX : 1> c;
+  constexpr bool ADAPTIVE = plant_adaptive<M>;
+  PlantCarry<M> c;
   dopri5_init(c, sp.h0);
   if constexpr (TV) c.t0 = t0;
   if constexpr (ADAPTIVE && METHOD != SIM_MAP) {
@@ -1135,23 +1091,12 @@ __device__ __forceinline__ void rollout_body(const KP& kp, const SimParams& sp, 
       tk = t0 + c.t;
     }
     if (k == 0 || up_step != 0) {
-      const double* src = up + (int64_t)k * up_step + b * up_stride;
-#pragma unroll
-      for (int i = 0; i < NU + NP; ++i) upv[i] = src[i];
+      rollout_load_up<M>(up, up_step, up_stride, k, b, upv);
       c.have_k1 = false;   // the slope kept from the last step belongs to the previous interval's inputs
     }
     const double* u = upv;
     const double* p = upv + NU;
-    bool ok = true;
-    if (METHOD == SIM_DOPRI5 || (METHOD < 0 && sp.method == SIM_DOPRI5)) {
-      if constexpr (ADAPTIVE && METHOD != SIM_MAP) ok = dopri5_interval<M>(c, x, u, p, kp.dt, sp.rtol, sp.atol, sp.max_steps) == SIM_OK;
-    } else if constexpr (METHOD != SIM_DOPRI5) {
-      double xo[NX];
-      if (kp.continuous && !M::DISCRETE) model_step<M>(4, kp.n_sub, x, u, p, kp.dt, xo, NoExt(), tk);
-      else model_step<M>(kp.erk_order, kp.n_sub, x, u, p, kp.dt, xo, NoExt(), tk);
-#pragma unroll
-      for (int i = 0; i < NX; ++i) x[i] = xo[i];
-    }
+    const bool ok = plant_interval<M, METHOD>(kp, sp, c, x, u, p, tk);
     double* Xk = X + ((int64_t)(k + 1) * batch + b) * NX;
 #pragma unroll
     for (int i = 0; i < NX; ++i) Xk[i] = ok ? x[i] : nan;
@@ -1166,12 +1111,7 @@ __device__ __forceinline__ void rollout_body(const KP& kp, const SimParams& sp, 
       }
     }
   }
-  if (stats != nullptr) {
-    stats[b * 4 + 0] = c.status;
-    stats[b * 4 + 1] = c.n_acc;
-    stats[b * 4 + 2] = c.n_rej;
-    stats[b * 4 + 3] = c.n_rhs;
-  }
+  rollout_write_stats(stats, b, c);
   if constexpr (ADAPTIVE && METHOD != SIM_MAP) {
     if (hc != nullptr) hc[b] = c.h;
   }
@@ -1206,9 +1146,7 @@ __device__ __forceinline__ void rollout_bdf_body(const KP& kp, const SimParams& 
   const double nan = __builtin_nan("");
   for (int k = 0; k < steps; ++k) {
     if (k == 0 || !held) {
-      const double* src = up + (int64_t)k * up_step + b * up_stride;
-#pragma unroll
-      for (int i = 0; i < NU + NP; ++i) upv[i] = src[i];
+      rollout_load_up<M>(up, up_step, up_stride, k, b, upv);
       if (k > 0) {
         bdf_restart(c, kp.dt);
         if constexpr (TV) c.t0 = t0 + k * kp.dt;
@@ -1230,12 +1168,7 @@ __device__ __forceinline__ void rollout_bdf_body(const KP& kp, const SimParams& 
       }
     }
   }
-  if (stats != nullptr) {
-    stats[b * 4 + 0] = c.status;
-    stats[b * 4 + 1] = c.n_acc;
-    stats[b * 4 + 2] = c.n_rej;
-    stats[b * 4 + 3] = c.n_rhs;
-  }
+  rollout_write_stats(stats, b, c);
 }
 
 // The SIM_IDAS path: rollout_bdf_body for a model with algebraic states (idas_interval in w = [x; z]).  z0 [batch][NZ] or null: the
@@ -1270,9 +1203,7 @@ __device__ __forceinline__ void rollout_idas_body(const KP& kp, const SimParams&
   const double nan = __builtin_nan("");
   for (int k = 0; k < steps; ++k) {
     if (k == 0 || !held) {
-      const double* src = up + (int64_t)k * up_step + b * up_stride;
-#pragma unroll
-      for (int i = 0; i < NU + NP; ++i) upv[i] = src[i];
+      rollout_load_up<M>(up, up_step, up_stride, k, b, upv);
       if (k > 0) bdf_restart(c, kp.dt);
     }
     const double* u = upv;
@@ -1303,18 +1234,13 @@ __device__ __forceinline__ void rollout_idas_body(const KP& kp, const SimParams&
       }
     }
   }
-  if (stats != nullptr) {
-    stats[b * 4 + 0] = c.status;
-    stats[b * 4 + 1] = c.n_acc;
-    stats[b * 4 + 2] = c.n_rej;
-    stats[b * 4 + 3] = c.n_rhs;
-  }
+  rollout_write_stats(stats, b, c);
 }
 
 // ---- forward sensitivities of the Dormand-Prince roll-out, one instance on a team of lanes -------------------------------------
 // `dopri5_sens_interval` integrates the augmented system
 //   dx/dt = f(t, x, u, p),   dS/dt = f_x S + f_theta,   theta = [x0; u; p],   S(0) = [I | 0 | 0]
-// with the pair, the controller and every convention of `dopri5_interval` above (stage times, first same as last, clipping at the
+// with the pair, the controller and every convention of `dopri5_interval` above - the same `dopri5_core`, on duals - (stage times, first same as last, clipping at the
 // sampling instant, model_ode_at): what scipy's RK45 does when it is handed the vector [x; vec S].  The error norm and the norms
 // of the first-step estimate run over all NX (1 + NS) components, each with its own scale atol + rtol max(|.|, |.+|); n_rhs counts
 // one evaluation of the augmented right-hand side as one, so n_rhs == 6 (acc + rej) + 2 holds as before.
@@ -1365,20 +1291,11 @@ constexpr int SENS_MAX_NX = 4;
 constexpr int SENS_X0 = 1, SENS_U = 2, SENS_P = 4;   // HILO_SENS_*: the groups of theta whose columns are carried, in this order
 
 template <int NX, int NC>
-struct SensCarry {   // Dopri5Carry with the slope at the current state as duals
-  Dual<NC> k1[NX];
-  double h, t, t0;
-  int status, n_acc, n_rej, n_rhs;
-  bool have_k1;
-};
+using SensCarry = Dopri5Carry<NX, Dual<NC>>;   // the slope at the current state as duals
 
 template <int NX, int NC>
 HD void sens_init(SensCarry<NX, NC>& c, double h0) {
-  c.h = h0 > 0.0 ? h0 : 0.0;
-  c.t = c.t0 = 0.0;
-  c.status = SIM_OK;
-  c.n_acc = c.n_rej = c.n_rhs = 0;
-  c.have_k1 = false;
+  dopri5_init(c, h0);
 }
 
 // The seeds of the lane (or host "lane") whose first column is col0: x gets its values and the unit tangents of the x0 group,
@@ -1432,107 +1349,30 @@ HD double sens_sumsq(const TEAM& team, const Dual<NC>* v, const Dual<NC>* a, con
   return sx + team.sum(sc);
 }
 
-// One sampling interval of the augmented system, in place in x (values and columns).  ns: the number of selected columns (the
-// norms' divisor is NX (1 + ns)); u, p: the inputs and parameters with their seeds.  Returns c.status, the same in every lane of a
-// team; on a failure x holds whatever the integration stopped at (the caller discards it).
+// the norm policy of the augmented vector (PlainNorm's sibling): NX (1 + ns) components, the columns' share through team.sum
+template <int NX, int NC, class TEAM>
+struct SensNorm {
+  const TEAM& team;
+  int ns;
+  double rtol, atol;
+  template <class V>
+  HD double sumsq(const V& v, const Dual<NC>* a, const Dual<NC>* b) const {
+    Dual<NC> w[NX];   // (a Lazy is written out first: the vector, then its sum, as the kernel had it)
+#pragma unroll
+    for (int i = 0; i < NX; ++i) w[i] = v[i];
+    return sens_sumsq<NX>(team, w, a, b, rtol, atol);
+  }
+  HD double divisor() const { return (double)(NX * (1 + ns)); }
+};
+
+// One sampling interval of the augmented system, in place in x (values and columns): dopri5_core on duals.  ns: the number of
+// selected columns (the norms' divisor is NX (1 + ns)); u, p: the inputs and parameters with their seeds.  Returns c.status, the
+// same in every lane of a team (tl, c.h and the step count are team-uniform); on a failure x holds whatever the integration
+// stopped at (the caller discards it).
 template <class M, int NC, class TEAM>
 HD int dopri5_sens_interval(SensCarry<M::NX, NC>& c, const TEAM& team, int ns, Dual<NC>* x, const Dual<NC>* u, const Dual<NC>* p,
                             double dt, double rtol, double atol, int max_steps) {
-  constexpr int NX = M::NX;
-  using D = Dual<NC>;
-  constexpr double EPS = 2.220446049250313e-16;
-  constexpr double A21 = 1.0 / 5;
-  constexpr double A31 = 3.0 / 40, A32 = 9.0 / 40;
-  constexpr double A41 = 44.0 / 45, A42 = -56.0 / 15, A43 = 32.0 / 9;
-  constexpr double A51 = 19372.0 / 6561, A52 = -25360.0 / 2187, A53 = 64448.0 / 6561, A54 = -212.0 / 729;
-  constexpr double A61 = 9017.0 / 3168, A62 = -355.0 / 33, A63 = 46732.0 / 5247, A64 = 49.0 / 176, A65 = -5103.0 / 18656;
-  constexpr double B1 = 35.0 / 384, B3 = 500.0 / 1113, B4 = 125.0 / 192, B5 = -2187.0 / 6784, B6 = 11.0 / 84;
-  constexpr double E1 = -71.0 / 57600, E3 = 71.0 / 16695, E4 = -71.0 / 1920, E5 = 17253.0 / 339200, E6 = -22.0 / 525, E7 = 1.0 / 40;
-  constexpr bool TV = model_time_variant<M>::value;
-  constexpr double C2 = 1.0 / 5, C3 = 3.0 / 10, C4 = 4.0 / 5, C5 = 8.0 / 9;
-  const double n_aug = (double)(NX * (1 + ns));
-  double ts = 0.0;   // absolute time at the start of this interval (time-variant functors only)
-  if constexpr (TV) ts = c.t0 + c.t;
-  auto f = [&](double at_t, const D* at, D* k) {
-    model_ode_at<M>(at_t, at, u, p, dt, k);
-    ++c.n_rhs;
-  };
-  if (c.status != SIM_OK) return c.status;
-  if (!c.have_k1) {
-    f(ts, x, c.k1);
-    c.have_k1 = true;
-  }
-  if (!(c.h > 0.0)) {   // the first step of the roll-out: dopri5_interval's estimate over the augmented vector
-    D x1[NX], f1[NX];
-    const double d0 = ::sqrt(sens_sumsq<NX>(team, x, x, x, rtol, atol) / n_aug);
-    const double d1 = ::sqrt(sens_sumsq<NX>(team, c.k1, x, x, rtol, atol) / n_aug);
-    double h0 = (d0 < 1e-5 || d1 < 1e-5) ? 1e-6 : 0.01 * d0 / d1;
-    h0 = ::fmin(h0, dt);
-#pragma unroll
-    for (int i = 0; i < NX; ++i) x1[i] = x[i] + h0 * c.k1[i];
-    f(ts + h0, x1, f1);
-#pragma unroll
-    for (int i = 0; i < NX; ++i) f1[i] = f1[i] - c.k1[i];
-    const double d2 = ::sqrt(sens_sumsq<NX>(team, f1, x, x, rtol, atol) / n_aug) / h0;
-    const double h1 = (d1 <= 1e-15 && d2 <= 1e-15) ? ::fmax(1e-6, h0 * 1e-3) : ::pow(0.01 / ::fmax(d1, d2), 0.2);
-    c.h = ::fmin(::fmin(100.0 * h0, h1), dt);
-    if (!(c.h > 0.0)) c.h = dt;   // a non-finite estimate: the controller below finds the step (or fails)
-  }
-  double tl = 0.0;          // time inside this interval
-  bool rejected = false;    // the previous attempt of the CURRENT step was rejected
-  int attempts = 0;
-  while (tl < dt) {         // (tl, c.h, attempts: team-uniform)
-    if (attempts >= max_steps) return c.status = SIM_MAX_STEPS;
-    if constexpr (TV) {
-      if (c.h < 16.0 * EPS * ::fabs(ts + tl)) return c.status = SIM_STEP_TOO_SMALL;
-    } else {
-      if (c.h < 16.0 * EPS * ::fabs(c.t + tl)) return c.status = SIM_STEP_TOO_SMALL;
-    }
-    ++attempts;
-    const double rem = dt - tl;
-    const bool last = 1.01 * c.h >= rem;
-    const double h = last ? rem : c.h;
-    D k2[NX], k3[NX], k4[NX], k5[NX], k6[NX], k7[NX], xi[NX], xn[NX];
-    double tn = 0.0;   // absolute time at the start of this step
-    if constexpr (TV) tn = ts + tl;
-#pragma unroll
-    for (int i = 0; i < NX; ++i) xi[i] = x[i] + h * (A21 * c.k1[i]);
-    f(tn + C2 * h, xi, k2);
-#pragma unroll
-    for (int i = 0; i < NX; ++i) xi[i] = x[i] + h * (A31 * c.k1[i] + A32 * k2[i]);
-    f(tn + C3 * h, xi, k3);
-#pragma unroll
-    for (int i = 0; i < NX; ++i) xi[i] = x[i] + h * (A41 * c.k1[i] + A42 * k2[i] + A43 * k3[i]);
-    f(tn + C4 * h, xi, k4);
-#pragma unroll
-    for (int i = 0; i < NX; ++i) xi[i] = x[i] + h * (A51 * c.k1[i] + A52 * k2[i] + A53 * k3[i] + A54 * k4[i]);
-    f(tn + C5 * h, xi, k5);
-#pragma unroll
-    for (int i = 0; i < NX; ++i) xi[i] = x[i] + h * (A61 * c.k1[i] + A62 * k2[i] + A63 * k3[i] + A64 * k4[i] + A65 * k5[i]);
-    f(tn + h, xi, k6);
-#pragma unroll
-    for (int i = 0; i < NX; ++i) xn[i] = x[i] + h * (B1 * c.k1[i] + B3 * k3[i] + B4 * k4[i] + B5 * k5[i] + B6 * k6[i]);
-    f(last ? ts + dt : tn + h, xn, k7);
-#pragma unroll
-    for (int i = 0; i < NX; ++i) xi[i] = h * (E1 * c.k1[i] + E3 * k3[i] + E4 * k4[i] + E5 * k5[i] + E6 * k6[i] + E7 * k7[i]);   // (xi: the error estimate)
-    const double err = ::sqrt(sens_sumsq<NX>(team, xi, x, xn, rtol, atol) / n_aug);   // the step's one cross-lane value
-    if (err < 1.0) {   // accepted (a non-finite estimate fails this comparison: a rejection)
-      double fac = err == 0.0 ? 10.0 : ::fmin(10.0, 0.9 * ::pow(err, -0.2));
-      if (rejected) fac = ::fmin(1.0, fac);
-      c.h = last ? ::fmax(c.h, h * fac) : h * fac;
-      tl = last ? dt : tl + h;
-#pragma unroll
-      for (int i = 0; i < NX; ++i) { x[i] = xn[i]; c.k1[i] = k7[i]; }
-      ++c.n_acc;
-      rejected = false;
-    } else {
-      c.h = h * ::fmax(0.2, 0.9 * ::pow(err, -0.2));   // (NaN or inf: fmax answers 0.2)
-      ++c.n_rej;
-      rejected = true;
-    }
-  }
-  c.t += dt;
-  return c.status;
+  return dopri5_core<M>(c, SensNorm<M::NX, NC, TEAM>{team, ns, rtol, atol}, x, u, p, dt, max_steps);
 }
 
 // The roll-out with sensitivities: 64 / T instances per wave, lane c of a team carries x and column c (NC = 1).  wrt: HILO_SENS_*
@@ -1581,9 +1421,7 @@ __device__ __forceinline__ void rollout_sens_body(const KP& kp, const SimParams&
       tk = t0 + c.t;
     }
     if (k == 0 || up_step != 0) {
-      const double* src = up + (int64_t)k * up_step + b * up_stride;
-#pragma unroll
-      for (int i = 0; i < NU + NP; ++i) upv[i] = src[i];
+      rollout_load_up<M>(up, up_step, up_stride, k, b, upv);
       sens_seed_up<M>(wrt, col, upv, u, p);
       c.have_k1 = false;   // the slope kept from the last step belongs to the previous interval's inputs
     }
@@ -1607,11 +1445,6 @@ __device__ __forceinline__ void rollout_sens_body(const KP& kp, const SimParams&
       }
     }
   }
-  if (stats != nullptr && first) {
-    stats[b * 4 + 0] = c.status;
-    stats[b * 4 + 1] = c.n_acc;
-    stats[b * 4 + 2] = c.n_rej;
-    stats[b * 4 + 3] = c.n_rhs;
-  }
+  if (first) rollout_write_stats(stats, b, c);
 }
 }  // namespace hilo

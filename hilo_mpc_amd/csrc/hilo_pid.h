@@ -63,7 +63,7 @@ HD double pid_update(double* m, double pv, double sp, double k_p, double t_i, do
 //   u_j   pid_update with this interval's set point; the driven entries of the input vector are overwritten, the others keep the
 //         held value
 //   plant model_step (SIM_MAP) or dopri5_interval (SIM_DOPRI5; the input jumps, so the slope kept from the last step is dropped
-//         every interval - the step-size proposal is carried) exactly as in rollout_body
+//         every interval - the step-size proposal is carried): rollout_body's plant_interval
 //   X[k + 1], U[k] (the nsp controller outputs), Y[k] = h(x[k + 1], u[k], p); each of X, U, Y may be null (the sweep: only J,
 //   x_final and stats leave the chip)
 //   J [batch][nsp][4]: ISE += e^2 dt, IAE += |e| dt, ITAE += (k dt) |e| dt, TVU += |u_k - u_{k-1}|, in k order
@@ -91,11 +91,7 @@ HD void pid_loop_instance(const KP& kp, const SimParams& sp, const PidParams& po
     x[i] = x0[b * NX + i];
     if (X != nullptr) X[b * NX + i] = x[i];
   }
-  {
-    const double* src = up + b * up_stride;
-#pragma unroll
-    for (int i = 0; i < NU + NP; ++i) upv[i] = src[i];
-  }
+  rollout_load_up<M>(up, 0, up_stride, 0, b, upv);   // held
   bool any_meas = false;
 #pragma unroll
   for (int j = 0; j < NL; ++j) {
@@ -112,8 +108,8 @@ HD void pid_loop_instance(const KP& kp, const SimParams& sp, const PidParams& po
       for (int i = 0; i < NU; ++i) upv[i] = po.out_index[j] == i ? m[j][4] : upv[i];
     }
   }
-  constexpr bool ADAPTIVE = !M::DISCRETE && NX <= DOPRI5_MAX_NX;
-  Dopri5Carry<ADAPTIVE ? NX : 1> c;
+  constexpr bool ADAPTIVE = plant_adaptive<M>;
+  PlantCarry<M> c;
   dopri5_init(c, sp.h0);
   if constexpr (TV) c.t0 = t0;
   if constexpr (ADAPTIVE && METHOD != SIM_MAP) {
@@ -162,15 +158,7 @@ HD void pid_loop_instance(const KP& kp, const SimParams& sp, const PidParams& po
         }
       }
       c.have_k1 = false;   // the input has jumped: the slope kept from the last step belongs to the previous interval
-      if (METHOD == SIM_DOPRI5 || (METHOD < 0 && sp.method == SIM_DOPRI5)) {
-        if constexpr (ADAPTIVE && METHOD != SIM_MAP) ok = dopri5_interval<M>(c, x, upv, p, kp.dt, sp.rtol, sp.atol, sp.max_steps) == SIM_OK;
-      } else if constexpr (METHOD != SIM_DOPRI5) {
-        double xo[NX];
-        if (kp.continuous && !M::DISCRETE) model_step<M>(4, kp.n_sub, x, upv, p, kp.dt, xo, NoExt(), tk);
-        else model_step<M>(kp.erk_order, kp.n_sub, x, upv, p, kp.dt, xo, NoExt(), tk);
-#pragma unroll
-        for (int i = 0; i < NX; ++i) x[i] = xo[i];
-      }
+      ok = plant_interval<M, METHOD>(kp, sp, c, x, upv, p, tk);
     } else if (U != nullptr) {
       for (int j = 0; j < nsp; ++j) U[((int64_t)k * batch + b) * nsp + j] = nan;
     }
@@ -203,12 +191,7 @@ HD void pid_loop_instance(const KP& kp, const SimParams& sp, const PidParams& po
   }
 #pragma unroll
   for (int i = 0; i < NX; ++i) x_final[b * NX + i] = ok ? x[i] : nan;
-  if (stats != nullptr) {
-    stats[b * 4 + 0] = c.status;
-    stats[b * 4 + 1] = c.n_acc;
-    stats[b * 4 + 2] = c.n_rej;
-    stats[b * 4 + 3] = c.n_rhs;
-  }
+  rollout_write_stats(stats, b, c);
   if constexpr (ADAPTIVE && METHOD != SIM_MAP) {
     if (hc != nullptr) hc[b] = c.h;
   }

@@ -83,24 +83,46 @@ static_assert(HILO_SIM_DOPRI5_MAX_NX == DOPRI5_MAX_NX && HILO_SIM_DOPRI5 == SIM_
               HILO_SENS_X0 == SENS_X0 && HILO_SENS_U == SENS_U && HILO_SENS_P == SENS_P,
               "include/hilo_hip.h and csrc/hilo_integrate.h disagree");
 
+// What the three entry points below share; `who` is the entry point's name, so that every message reads as it did.
+// SimParams and the time of row 0 of X (read by a time-variant model only) from the caller's options (NULL: the defaults)
+static int sim_options(const char* who, const hilo_sim_opts* opts, SimParams* sp, double* t0) {
+  *sp = {SIM_MAP, 10000, 1e-6, 1e-8, 0.0};
+  *t0 = 0.0;
+  if (!opts) return HILO_OK;
+  sp->method = opts->method;
+  if (opts->max_steps > 0) sp->max_steps = opts->max_steps;
+  if (opts->rtol > 0.0) sp->rtol = opts->rtol;
+  if (opts->atol > 0.0) sp->atol = opts->atol;
+  if (opts->h0 > 0.0) sp->h0 = opts->h0;
+  HILO_REQUIRE(opts->t0 == opts->t0 && ::fabs(opts->t0) < INFINITY, "%s: t0 must be finite", who);
+  *t0 = opts->t0;
+  return HILO_OK;
+}
+
+// the checks of a non-empty batch's arguments (`pointers`: the entry point's own required ones are there); a NULL `up` leaves
+// pointing at a stand-in
+static int sim_check_args(const char* who, const hilo_kf* kf, int64_t batch, bool pointers, const double** up, int64_t up_stride,
+                          int64_t up_step) {
+  HILO_REQUIRE(pointers, "%s: NULL argument", who);
+  HILO_REQUIRE(kf->nu + kf->np == 0 || *up, "%s: the model has %d inputs/parameters but `up` is NULL", who, kf->nu + kf->np);
+  HILO_REQUIRE(up_stride == 0 || up_stride >= kf->nu + kf->np, "%s: up_stride %lld < nu+np", who, (long long)up_stride);
+  HILO_REQUIRE(up_step == 0 || up_step >= (up_stride ? batch * up_stride : kf->nu + kf->np),
+               "%s: up_step %lld is shorter than one sampling interval's rows", who, (long long)up_step);
+  static const double zero = 0.0;
+  if (!*up) *up = &zero;   // never read (nu + np == 0); keeps the pointer arithmetic of the kernel defined
+  return HILO_OK;
+}
+
 // hilo_model_rollout (h NULL) and hilo_model_rollout_resume
 static int rollout_impl(hilo_kf* kf, const hilo_sim_opts* opts, int64_t batch, int steps, const double* x0, const double* up,
                         int64_t up_stride, int64_t up_step, double* X, double* Y, int32_t* stats, double* h, void* stream) {
   HILO_REQUIRE(kf, "hilo_model_rollout: NULL handle");
   HILO_REQUIRE(batch >= 0 && steps >= 1, "hilo_model_rollout: need batch >= 0 and steps >= 1");
-  SimParams sp = {SIM_MAP, 10000, 1e-6, 1e-8, 0.0};
-  double t0 = 0.0;   // the time of row 0 of X (read by a time-variant model only)
-  if (opts) {
-    HILO_REQUIRE(opts->method == HILO_SIM_MAP || opts->method == HILO_SIM_DOPRI5 || opts->method == HILO_SIM_BDF,
-                 "hilo_model_rollout: unknown method %d", opts->method);
-    sp.method = opts->method;
-    if (opts->max_steps > 0) sp.max_steps = opts->max_steps;
-    if (opts->rtol > 0.0) sp.rtol = opts->rtol;
-    if (opts->atol > 0.0) sp.atol = opts->atol;
-    if (opts->h0 > 0.0) sp.h0 = opts->h0;
-    HILO_REQUIRE(opts->t0 == opts->t0 && ::fabs(opts->t0) < INFINITY, "hilo_model_rollout: t0 must be finite");
-    t0 = opts->t0;
-  }
+  HILO_REQUIRE(!opts || opts->method == HILO_SIM_MAP || opts->method == HILO_SIM_DOPRI5 || opts->method == HILO_SIM_BDF,
+               "hilo_model_rollout: unknown method %d", opts->method);
+  SimParams sp;
+  double t0;
+  if (int rc = sim_options("hilo_model_rollout", opts, &sp, &t0)) return rc;
   if (sp.method == SIM_DOPRI5) {
     if (kf->discrete || !kf->kp.continuous)
       return fail(HILO_ENOTSUP, "hilo_model_rollout: HILO_SIM_DOPRI5 integrates a continuous model; this handle holds a discrete "
@@ -128,16 +150,10 @@ static int rollout_impl(hilo_kf* kf, const hilo_sim_opts* opts, int64_t batch, i
     return fail(HILO_ENOTSUP, "hilo_model_rollout_resume: the step-size proposal is handed on by the kernels of a run-time compiled "
                               "model; this handle holds a model of the zoo (pass h = NULL)");
   if (batch == 0) return HILO_OK;
-  HILO_REQUIRE(x0 && X, "hilo_model_rollout: NULL argument");
-  HILO_REQUIRE(kf->nu + kf->np == 0 || up, "hilo_model_rollout: the model has %d inputs/parameters but `up` is NULL", kf->nu + kf->np);
-  HILO_REQUIRE(up_stride == 0 || up_stride >= kf->nu + kf->np, "hilo_model_rollout: up_stride %lld < nu+np", (long long)up_stride);
-  HILO_REQUIRE(up_step == 0 || up_step >= (up_stride ? batch * up_stride : kf->nu + kf->np),
-               "hilo_model_rollout: up_step %lld is shorter than one sampling interval's rows", (long long)up_step);
+  if (int rc = sim_check_args("hilo_model_rollout", kf, batch, x0 && X, &up, up_stride, up_step)) return rc;
   HILO_HIP_CHECK(hipSetDevice(kf->device));
   hipStream_t s = (hipStream_t)stream;
   const KfParams& kp = kf->kp;
-  static const double zero = 0.0;
-  if (!up) up = &zero;   // never read (nu + np == 0); keeps the pointer arithmetic of the kernel defined
   int* st = (int*)stats;
   if (kf->desc.model_id == 100 /* HILO_MODEL_USER */) {
     hipFunction_t fn = sp.method == SIM_BDF ? kf->jit.rollout_bdf : kf->jit.rollout;
@@ -173,15 +189,9 @@ extern "C" int hilo_model_rollout_dae(hilo_kf* kf, const hilo_sim_opts* opts, in
                                       double* Y, int32_t* stats, void* stream) {
   HILO_REQUIRE(kf, "hilo_model_rollout_dae: NULL handle");
   HILO_REQUIRE(batch >= 0 && steps >= 1, "hilo_model_rollout_dae: need batch >= 0 and steps >= 1");
-  SimParams sp = {SIM_MAP, 10000, 1e-6, 1e-8, 0.0};
-  if (opts) {
-    sp.method = opts->method;
-    if (opts->max_steps > 0) sp.max_steps = opts->max_steps;
-    if (opts->rtol > 0.0) sp.rtol = opts->rtol;
-    if (opts->atol > 0.0) sp.atol = opts->atol;
-    if (opts->h0 > 0.0) sp.h0 = opts->h0;
-    HILO_REQUIRE(opts->t0 == opts->t0 && ::fabs(opts->t0) < INFINITY, "hilo_model_rollout_dae: t0 must be finite");
-  }
+  SimParams sp;
+  double t0;   // (no kernel of a DAE reads it)
+  if (int rc = sim_options("hilo_model_rollout_dae", opts, &sp, &t0)) return rc;
   if (sp.method != SIM_IDAS)
     return fail(HILO_ENOTSUP, "hilo_model_rollout_dae: method %d; this entry integrates with HILO_SIM_IDAS alone (the other methods: "
                               "hilo_model_rollout)", sp.method);
@@ -200,14 +210,8 @@ extern "C" int hilo_model_rollout_dae(hilo_kf* kf, const hilo_sim_opts* opts, in
     return fail(HILO_ENOTSUP, "hilo_model_rollout_dae: the compiled equations of this model leave HILO_SIM_IDAS %d bytes of scratch "
                               "memory per lane; the method is built to keep its vectors in registers", kf->jit.rollout_idas_scratch);
   if (batch == 0) return HILO_OK;
-  HILO_REQUIRE(x0 && X, "hilo_model_rollout_dae: NULL argument");
-  HILO_REQUIRE(kf->nu + kf->np == 0 || up, "hilo_model_rollout_dae: the model has %d inputs/parameters but `up` is NULL", kf->nu + kf->np);
-  HILO_REQUIRE(up_stride == 0 || up_stride >= kf->nu + kf->np, "hilo_model_rollout_dae: up_stride %lld < nu+np", (long long)up_stride);
-  HILO_REQUIRE(up_step == 0 || up_step >= (up_stride ? batch * up_stride : kf->nu + kf->np),
-               "hilo_model_rollout_dae: up_step %lld is shorter than one sampling interval's rows", (long long)up_step);
+  if (int rc = sim_check_args("hilo_model_rollout_dae", kf, batch, x0 && X, &up, up_stride, up_step)) return rc;
   HILO_HIP_CHECK(hipSetDevice(kf->device));
-  static const double zero = 0.0;
-  if (!up) up = &zero;   // never read (nu + np == 0); keeps the pointer arithmetic of the kernel defined
   hipFunction_t fn = kf->jit.rollout_idas;
   HILO_REQUIRE(fn, "hilo_model_rollout_dae: the run-time compiled roll-out kernel is not loaded");
   KfParams kpv = kf->kp;
@@ -231,17 +235,9 @@ extern "C" int hilo_model_rollout_sens(hilo_kf* kf, const hilo_sim_opts* opts, i
                                        double* SX, double* SY, int32_t* stats, void* stream) {
   HILO_REQUIRE(kf, "hilo_model_rollout_sens: NULL handle");
   HILO_REQUIRE(batch >= 0 && steps >= 1, "hilo_model_rollout_sens: need batch >= 0 and steps >= 1");
-  SimParams sp = {SIM_MAP, 10000, 1e-6, 1e-8, 0.0};
-  double t0 = 0.0;
-  if (opts) {
-    sp.method = opts->method;
-    if (opts->max_steps > 0) sp.max_steps = opts->max_steps;
-    if (opts->rtol > 0.0) sp.rtol = opts->rtol;
-    if (opts->atol > 0.0) sp.atol = opts->atol;
-    if (opts->h0 > 0.0) sp.h0 = opts->h0;
-    HILO_REQUIRE(opts->t0 == opts->t0 && ::fabs(opts->t0) < INFINITY, "hilo_model_rollout_sens: t0 must be finite");
-    t0 = opts->t0;
-  }
+  SimParams sp;
+  double t0;
+  if (int rc = sim_options("hilo_model_rollout_sens", opts, &sp, &t0)) return rc;
   const bool user = kf->desc.model_id == 100 /* HILO_MODEL_USER */;
   if (sp.method != SIM_DOPRI5)
     return fail(HILO_ENOTSUP, "hilo_model_rollout_sens: method %d; the sensitivities are integrated with HILO_SIM_DOPRI5 alone (the "
@@ -270,11 +266,7 @@ extern "C" int hilo_model_rollout_sens(hilo_kf* kf, const hilo_sim_opts* opts, i
     return fail(HILO_ENOTSUP, "hilo_model_rollout_sens: the compiled right-hand side of this model leaves the sensitivity kernel %d "
                               "bytes of scratch memory per lane; it is built to keep its vectors in registers", kf->jit.rollout_sens_scratch);
   if (batch == 0) return HILO_OK;
-  HILO_REQUIRE(x0 && X && SX, "hilo_model_rollout_sens: NULL argument");
-  HILO_REQUIRE(kf->nu + kf->np == 0 || up, "hilo_model_rollout_sens: the model has %d inputs/parameters but `up` is NULL", kf->nu + kf->np);
-  HILO_REQUIRE(up_stride == 0 || up_stride >= kf->nu + kf->np, "hilo_model_rollout_sens: up_stride %lld < nu+np", (long long)up_stride);
-  HILO_REQUIRE(up_step == 0 || up_step >= (up_stride ? batch * up_stride : kf->nu + kf->np),
-               "hilo_model_rollout_sens: up_step %lld is shorter than one sampling interval's rows", (long long)up_step);
+  if (int rc = sim_check_args("hilo_model_rollout_sens", kf, batch, x0 && X && SX, &up, up_stride, up_step)) return rc;
   int T = 1;
   while (T < ns) T <<= 1;   // the smallest power of two >= ns
   const int per_wave = ROLLOUT_TPB / T;
@@ -284,8 +276,6 @@ extern "C" int hilo_model_rollout_sens(hilo_kf* kf, const hilo_sim_opts* opts, i
   HILO_HIP_CHECK(hipSetDevice(kf->device));
   hipStream_t s = (hipStream_t)stream;
   const KfParams& kp = kf->kp;
-  static const double zero = 0.0;
-  if (!up) up = &zero;   // never read (nu + np == 0); keeps the pointer arithmetic of the kernel defined
   int* st = (int*)stats;
   if (user) {
     hipFunction_t fn = kf->jit.rollout_sens;

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Register / scratch / LDS figures of every kernel in libhilo_hip.so (or the library given), from the code objects' metadata.
-    python tools/kernel_resources.py [lib.so] [substring ...]
+"""Register / scratch / LDS figures of every kernel in libhilo_hip.so (or the library given), from the code objects' metadata;
+a .hsaco of the run-time compiler's cache is read as the one code object it is.
+    python tools/kernel_resources.py [lib.so | file.hsaco] [substring ...]
 """
 import os
 import re
@@ -9,14 +10,19 @@ import sys
 import tempfile
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-lib = sys.argv[1] if len(sys.argv) > 1 and sys.argv[1].endswith('.so') else os.path.join(HERE, '..', 'hilo_mpc_amd', 'libhilo_hip.so')
-keys = [a for a in sys.argv[1:] if not a.endswith('.so')]
+given = len(sys.argv) > 1 and sys.argv[1].endswith(('.so', '.hsaco'))
+lib = sys.argv[1] if given else os.path.join(HERE, '..', 'hilo_mpc_amd', 'libhilo_hip.so')
+keys = sys.argv[2:] if given else sys.argv[1:]
 BIN = '/opt/rocm/lib/llvm/bin'
-with tempfile.TemporaryDirectory() as td:
-    data = open(lib, 'rb').read()
+
+
+def code_objects(path, td):
+    if path.endswith('.hsaco'):
+        yield path
+        return
+    data = open(path, 'rb').read()
     # the bundles: concatenated "__CLANG_OFFLOAD_BUNDLE__" blobs inside .hip_fatbin; unbundle each by offset
     offs = [m.start() for m in re.finditer(b'__CLANG_OFFLOAD_BUNDLE__', data)]
-    rows = []
     for n, o in enumerate(offs):
         end = offs[n + 1] if n + 1 < len(offs) else len(data)
         blob = os.path.join(td, f'b{n}.bin')
@@ -24,8 +30,13 @@ with tempfile.TemporaryDirectory() as td:
         co = os.path.join(td, f'b{n}.co')
         r = subprocess.run([f'{BIN}/clang-offload-bundler', '--unbundle', '--type=o', f'--input={blob}', f'--output={co}',
                             '--targets=hipv4-amdgcn-amd-amdhsa--gfx950'], capture_output=True, text=True)
-        if r.returncode or not os.path.exists(co) or os.path.getsize(co) == 0:
-            continue
+        if r.returncode == 0 and os.path.exists(co) and os.path.getsize(co) > 0:
+            yield co
+
+
+with tempfile.TemporaryDirectory() as td:
+    rows = []
+    for co in code_objects(lib, td):
         notes = subprocess.run([f'{BIN}/llvm-readelf', '--notes', co], capture_output=True, text=True).stdout
         for blk in notes.split('  - .agpr_count:')[1:]:
             get = lambda k: (re.search(rf'\.{k}:\s+(\S+)', blk) or [None, '?'])[1]   # noqa: E731
