@@ -41,6 +41,12 @@ class PidOpts(C.Structure):
                 ('out_index', C.c_int32 * 4), ('lo', C.c_double * 4), ('hi', C.c_double * 4)]
 
 
+class PfOpts(C.Structure):
+    """hilo_pf_opts: flags 1 = systematic resampling, 2 = roughening (K)."""
+    _fields_ = [('seed', C.c_uint64), ('step0', C.c_int64), ('filter_offset', C.c_int64), ('flags', C.c_int32),
+                ('reserved', C.c_int32), ('K', C.c_double)]
+
+
 class LqrOpts(C.Structure):
     """hilo_lqr_opts: horizon 0 = stationary."""
     _fields_ = [('horizon', C.c_int32), ('max_iter', C.c_int32), ('tol', C.c_double)]
@@ -124,7 +130,9 @@ def _declare(lib):
         'hilo_lqr_apply': (C.c_int, [i32, i32, i64, vp, i64, vp, vp, vp, vp, vp]),
         'hilo_pf_stats': (C.c_int, [vp, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         'hilo_pf_resample': (C.c_int, [vp, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
-        'hilo_nmpc_create': (C.c_int, [P(NmpcDesc), i32, P(vp)]),
+        'hilo_pf_run': (C.c_int, [vp, P(PfOpts), i64, i32, i32, vp, vp, vp, vp, i64, i64, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp,
+                                  vp, vp, vp, vp]),
+        'hilo_nmpc_create':(C.c_int, [P(NmpcDesc), i32, P(vp)]),
         'hilo_nmpc_destroy': (None, [vp]),
         'hilo_nmpc_dims': (C.c_int, [vp, P(C.c_int), P(C.c_int), P(C.c_int), P(C.c_int), P(C.c_int)]),
         'hilo_nmpc_reset_warm_start': (C.c_int, [vp]),

@@ -55,6 +55,7 @@ void jit_unload(JitKernels* k);
 struct JitKfKernels {
   hipFunction_t f[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
   hipFunction_t pf = nullptr;   // particle-filter function of the same model (hilo_kf_kernel.h::pf_body)
+  hipFunction_t pf_run = nullptr;   // whole particle-filter runs with on-device draws (hilo_kf_kernel.h::pf_run_body)
   hipFunction_t multi[2] = {nullptr, nullptr};   // several fused steps per launch (kf_multi_body): [UKF]
   hipFunction_t team[2] = {nullptr, nullptr};    // the same on a team of lanes per instance (kf_team_body): small batches
   hipFunction_t rollout = nullptr;               // many sampling intervals per launch (hilo_integrate.h::rollout_body)

@@ -429,6 +429,25 @@ extern "C" __global__ __launch_bounds__(PF_TPB) void hilo_user_pf(KfParams kp, i
   pf_body<UserModel>(kp, n, X + b * n * NX, y + b * NYE, up + b * up_stride, w + b * n * NX, v + b * n * NYE, R + b * r_stride,
                      Xp + b * n * NX, Y + b * n * NYE, q + b * n);
 }
+extern "C" __global__ __launch_bounds__(PF_TPB) void hilo_user_pf_run(KfParams kp, PfRun o, int64_t batch, int n, int steps, double* X,
+                                                                      double* work, const double* __restrict__ y,
+                                                                      const double* __restrict__ up, int64_t up_stride,
+                                                                      int64_t up_step, const double* __restrict__ Q, int64_t q_stride,
+                                                                      const double* __restrict__ R, int64_t r_stride,
+                                                                      const double* __restrict__ x0, const double* __restrict__ P0,
+                                                                      double* __restrict__ x_out, double* __restrict__ P_out,
+                                                                      double* __restrict__ y_out, double* __restrict__ ess_out,
+                                                                      int* __restrict__ index_out, double* __restrict__ Xp_out,
+                                                                      double* __restrict__ Y_out, double* __restrict__ q_out,
+                                                                      int* __restrict__ status) {
+  extern __shared__ double pf_dyn[];
+  if (n <= PF_WAVE_N)
+    pf_run_body<UserModel, true>(kp, o, batch, n, steps, X, work, y, up, up_stride, up_step, Q, q_stride, R, r_stride, x0, P0, x_out,
+                                 P_out, y_out, ess_out, index_out, Xp_out, Y_out, q_out, status, pf_dyn);
+  else
+    pf_run_body<UserModel, false>(kp, o, batch, n, steps, X, work, y, up, up_stride, up_step, Q, q_stride, R, r_stride, x0, P0, x_out,
+                                  P_out, y_out, ess_out, index_out, Xp_out, Y_out, q_out, status, pf_dyn);
+}
 extern "C" __global__ __launch_bounds__(ROLLOUT_TPB) void hilo_user_rollout(KfParams kp, SimParams sp, int64_t batch, int steps,
                                                                             const double* __restrict__ x0,
                                                                             const double* __restrict__ up, int64_t up_stride,
@@ -530,6 +549,7 @@ extern "C" __global__ void hilo_user_kf_info(int* o) {
   for (int u = 0; u < 2; ++u)
     for (int m = 0; m < 3; ++m) HILO_HIP_CHECK(hipModuleGetFunction(&k.f[u][m], mod, names[u][m]));
   HILO_HIP_CHECK(hipModuleGetFunction(&k.pf, mod, "hilo_user_pf"));
+  HILO_HIP_CHECK(hipModuleGetFunction(&k.pf_run, mod, "hilo_user_pf_run"));
   HILO_HIP_CHECK(hipModuleGetFunction(&k.multi[0], mod, "hilo_user_kf_em"));
   HILO_HIP_CHECK(hipModuleGetFunction(&k.multi[1], mod, "hilo_user_kf_um"));
   HILO_HIP_CHECK(hipModuleGetFunction(&k.team[0], mod, "hilo_user_kf_et"));

@@ -482,3 +482,85 @@ extern "C" int hilo_pf_stats(hilo_kf* kf, int64_t batch, int n_samples, double* 
   HILO_HIP_CHECK(hipGetLastError());
   return HILO_OK;
 }
+
+// ---- particle filter with on-device random draws: `steps` steps of a batch of filters in ONE launch (hilo_kf_kernel.h::pf_run_body) ----
+namespace hilo {
+static size_t pf_run_lds(int n) { return sizeof(double) * (n <= PF_WAVE_N ? (size_t)PF_WAVE_N * (PF_TPB / 64) : (size_t)n); }
+static unsigned pf_run_grid(int64_t batch, int n) { return (unsigned)(n <= PF_WAVE_N ? (batch + PF_TPB / 64 - 1) / (PF_TPB / 64) : batch); }
+
+template <class M>
+static int pf_run_launch(const KfParams& kp, const PfRun& o, int64_t batch, int n, int steps, double* X, double* work, const double* y,
+                         const double* up, int64_t us, int64_t ustep, const double* Q, int64_t qs, const double* R, int64_t rs,
+                         const double* x0, const double* P0, double* x_out, double* P_out, double* y_out, double* ess_out, int* index_out,
+                         double* Xp_out, double* Y_out, double* q_out, int* status, hipStream_t s) {
+  const size_t lds = pf_run_lds(n);
+  if (lds + 8 * 1024 > 64 * 1024)      // (the static part: one Cholesky factor and the reduction slots)
+    HILO_HIP_CHECK(hipFuncSetAttribute((const void*)pf_run_kernel<M>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL((pf_run_kernel<M>), dim3(pf_run_grid(batch, n)), dim3(PF_TPB), lds, s, kp, o, batch, n, steps, X, work, y, up, us,
+                     ustep, Q, qs, R, rs, x0, P0, x_out, P_out, y_out, ess_out, index_out, Xp_out, Y_out, q_out, status);
+  HILO_HIP_CHECK(hipGetLastError());
+  return HILO_OK;
+}
+}  // namespace hilo
+
+extern "C" int hilo_pf_run(hilo_kf* kf, const hilo_pf_opts* opts, int64_t batch, int n_samples, int steps, double* X, double* work,
+                           const double* y, const double* up, int64_t up_stride, int64_t up_step, const double* Q, int64_t q_stride,
+                           const double* R, int64_t r_stride, const double* x0, const double* P0, double* x_out, double* P_out,
+                           double* y_out, double* ess_out, int32_t* index_out, double* X_prop_out, double* Y_out, double* q_out,
+                           int32_t* status, void* stream) {
+  HILO_REQUIRE(kf, "hilo_pf_run: NULL handle");
+  HILO_REFUSE_TIME_VARIANT(kf, "hilo_pf_run");
+  HILO_REQUIRE(opts, "hilo_pf_run: NULL options");
+  HILO_REQUIRE(batch >= 0 && steps >= 1, "hilo_pf_run: need batch >= 0 and steps >= 1");
+  HILO_REQUIRE(n_samples >= 2 && n_samples <= 8192, "hilo_pf_run: built for 2 to 8192 particles per filter, got %d", n_samples);
+  HILO_REQUIRE(kf->nx <= 16, "hilo_pf_run: built for up to 16 states, the model has %d", kf->nx);
+  HILO_REQUIRE((opts->flags & ~(HILO_PF_SYSTEMATIC | HILO_PF_ROUGHENING)) == 0, "hilo_pf_run: unknown flags 0x%x", (unsigned)opts->flags);
+  HILO_REQUIRE(opts->step0 >= 0 && opts->step0 + steps <= 0xffffffffLL, "hilo_pf_run: the step counter is a 32-bit word of the generator's counter");
+  HILO_REQUIRE(opts->filter_offset >= 0 && opts->filter_offset + batch <= 0xffffffffLL,
+               "hilo_pf_run: the filter number is a 32-bit word of the generator's counter");
+  HILO_REQUIRE(!(opts->flags & HILO_PF_ROUGHENING) || opts->K >= 0.0, "hilo_pf_run: the roughening parameter K must not be negative");
+  if (batch == 0) return HILO_OK;
+  HILO_REQUIRE(X && work && y && Q && R && x_out && P_out && y_out && ess_out && status, "hilo_pf_run: NULL argument");
+  HILO_REQUIRE(!P0 || x0, "hilo_pf_run: P0 asks for the initial sample, which needs x0");
+  HILO_REQUIRE(kf->nu + kf->np == 0 || up, "hilo_pf_run: the model has %d inputs/parameters but `up` is NULL", kf->nu + kf->np);
+  HILO_REQUIRE(up_stride == 0 || up_stride >= kf->nu + kf->np, "hilo_pf_run: up_stride %lld < nu+np", (long long)up_stride);
+  HILO_REQUIRE(up_step >= 0, "hilo_pf_run: negative up_step");
+  const int nye = kf->ny > 0 ? kf->ny : kf->nx;
+  HILO_REQUIRE(q_stride == 0 || q_stride >= kf->nx * kf->nx, "hilo_pf_run: bad q_stride");
+  HILO_REQUIRE(r_stride == 0 || r_stride >= nye * nye, "hilo_pf_run: bad r_stride");
+  HILO_HIP_CHECK(hipSetDevice(kf->device));
+  hipStream_t s = (hipStream_t)stream;
+  const KfParams& kp = kf->kp;
+  static const double zero = 0.0;
+  if (!up) { up = &zero; up_stride = up_step = 0; }   // never read (nu + np == 0); keeps the pointer arithmetic of the kernel defined
+  PfRun o;
+  o.key0 = (unsigned)(opts->seed & 0xffffffffu);
+  o.key1 = (unsigned)(opts->seed >> 32);
+  o.step0 = (unsigned)opts->step0;
+  o.filter0 = (unsigned)opts->filter_offset;
+  o.flags = opts->flags;
+  o.K = opts->K;
+  int* idx = (int*)index_out;
+  int* st = (int*)status;
+  if (kf->desc.model_id == 100 /* HILO_MODEL_USER */) {
+    HILO_REQUIRE(kf->jit.pf_run, "hilo_pf_run: the run-time compiled particle kernel is not loaded");
+    KfParams kpv = kp;
+    void* args[] = {&kpv, &o, &batch, &n_samples, &steps, &X, &work, &y, &up, &up_stride, &up_step, &Q, &q_stride, &R, &r_stride, &x0, &P0,
+                    &x_out, &P_out, &y_out, &ess_out, &idx, &X_prop_out, &Y_out, &q_out, &st};
+    HILO_HIP_CHECK(hipModuleLaunchKernel(kf->jit.pf_run, pf_run_grid(batch, n_samples), 1, 1, PF_TPB, 1, 1, (unsigned)pf_run_lds(n_samples), s,
+                                         args, nullptr));
+    return HILO_OK;
+  }
+  switch (kf->desc.model_id) {
+#define PF_RUN_ARGS kp, o, batch, n_samples, steps, X, work, y, up, up_stride, up_step, Q, q_stride, R, r_stride, x0, P0, x_out, P_out, y_out, ess_out, idx, X_prop_out, Y_out, q_out, st, s
+#define X_(ID, T) case ID: return pf_run_launch<T>(PF_RUN_ARGS);
+    HILO_KF_MODELS(X_)
+#undef X_
+    case HILO_MODEL_LTI:
+      if (kf->nx == 2 && kf->ny == 1) return pf_run_launch<Lti<2, 1, 1>>(PF_RUN_ARGS);
+      if (kf->nx == 2 && kf->ny == 2) return pf_run_launch<Lti<2, 1, 2>>(PF_RUN_ARGS);
+      return pf_run_launch<Lti<4, 2, 2>>(PF_RUN_ARGS);
+#undef PF_RUN_ARGS
+  }
+  return fail(HILO_EINVAL, "unknown model id %d", kf->desc.model_id);
+}

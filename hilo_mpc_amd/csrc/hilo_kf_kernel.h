@@ -1179,4 +1179,366 @@ __global__ __launch_bounds__(PF_TPB) void pf_stats_kernel(int n, int nx, int ny,
     }
 }
 
+// ---- particle filter with on-device random draws: whole runs in one launch ------------------------------------------------------
+// The flow of `ParticleFilter.estimate` (pf.py:340-422) for `steps` steps without the host: every random number is a pure function
+// of (seed, filter, absolute step, particle, purpose) - Philox4x32-10 (Salmon et al., SC'11) on the counter
+//     (j, k, b + filter_offset, stream << 16 | d)        key = (seed low, seed high)
+// with j the particle, k the absolute step, b the filter, d the block of two normals; streams: 0 initial sample (k = 0), 1 process
+// noise, 2 measurement noise, 3 resampling uniforms, 4 roughening.  A result therefore does not depend on the batch the filter runs
+// in, on the launch shape or on how a run is cut into calls.
+struct PfRun {
+  unsigned key0, key1;     // seed low / high
+  unsigned step0;          // absolute number of the first step of this launch
+  unsigned filter0;        // global number of filter 0 of this batch
+  int flags;               // PF_SYSTEMATIC | PF_ROUGHENING
+  double K;                // roughening tuning parameter (pf.py:412)
+};
+constexpr int PF_SYSTEMATIC = 1, PF_ROUGHENING = 2;
+constexpr int PF_WAVE_N = 64;        // up to this many particles a filter is ONE wave, four filters per workgroup
+constexpr int PF_STATUS_NOT_FINITE = 1;
+
+struct Philox4 { unsigned r0, r1, r2, r3; };
+HD unsigned pf_mulhi(unsigned a, unsigned b) { return (unsigned)(((unsigned long long)a * b) >> 32); }
+HD Philox4 philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const unsigned h0 = pf_mulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0, h1 = pf_mulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
+    c0 = h1 ^ c1 ^ k0; c1 = l1; c2 = h0 ^ c3 ^ k1; c3 = l0;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  return Philox4{c0, c1, c2, c3};
+}
+// 53 bits of two words, centred in their cell: never 0, so the logarithm is safe (the topmost cell rounds to 1)
+HD double pf_uniform(unsigned a, unsigned b) {
+  return ((double)(((unsigned long long)(a >> 5) << 26) | (unsigned long long)(b >> 6)) + 0.5) * 0x1p-53;
+}
+// Box-Muller: block d supplies the normals 2d and 2d+1
+__device__ __forceinline__ void pf_normal_pair(const PfRun& o, unsigned j, unsigned k, unsigned b, unsigned stream, unsigned d, double& z0,
+                                               double& z1) {
+  const Philox4 r = philox4x32_10(j, k, b, stream << 16 | d, o.key0, o.key1);
+  const double rad = ::sqrt(-2.0 * ::log(pf_uniform(r.r0, r.r1)));
+  double s, c;
+  sin_cos(6.283185307179586 * pf_uniform(r.r2, r.r3), s, c);
+  z0 = rad * c;
+  z1 = rad * s;
+}
+template <int N>
+__device__ __forceinline__ void pf_normals(const PfRun& o, unsigned j, unsigned k, unsigned b, unsigned stream, double (&z)[N]) {
+  static_assert(N % 2 == 0, "pairs");
+#pragma unroll
+  for (int d = 0; d < N / 2; ++d) pf_normal_pair(o, j, k, b, stream, d, z[2 * d], z[2 * d + 1]);
+}
+// lower Cholesky factor of A [n][n] into L; a non-positive pivot zeroes its column (a covariance with unexcited states)
+__device__ inline void pf_cholesky(int n, const double* __restrict__ A, double* L) {
+  for (int j = 0; j < n; ++j) {
+    double s = A[j * n + j];
+    for (int k = 0; k < j; ++k) s -= L[j * n + k] * L[j * n + k];
+    const bool ok = s > 0.0;
+    const double d = ok ? ::sqrt(s) : 0.0;
+    for (int i = 0; i < j; ++i) L[i * n + j] = 0.0;
+    L[j * n + j] = d;
+    for (int i = j + 1; i < n; ++i) {
+      double t = A[i * n + j];
+      for (int k = 0; k < j; ++k) t -= L[i * n + k] * L[j * n + k];
+      L[i * n + j] = ok ? t / d : 0.0;
+    }
+  }
+}
+
+// the team of a filter: one wave (WAVE, no workgroup barrier anywhere) or the workgroup of four
+template <bool WAVE>
+__device__ __forceinline__ void pf_sync() {
+  if constexpr (WAVE) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  } else {
+    __syncthreads();
+  }
+}
+// OP 0 sum, 1 min, 2 max: butterfly over the wave's lanes (every lane ends with the same bits), then the four waves through LDS
+template <int OP>
+__device__ __forceinline__ double pf_op(double a, double b) { return OP == 0 ? a + b : (OP == 1 ? ::fmin(a, b) : ::fmax(a, b)); }
+template <bool WAVE, int OP, int K>
+__device__ __forceinline__ void pf_reduce(double (&v)[K], double* red) {
+#pragma unroll
+  for (int i = 0; i < K; ++i)
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v[i] = pf_op<OP>(v[i], __shfl_xor(v[i], o));
+  if constexpr (!WAVE) {
+    const int w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0)
+#pragma unroll
+      for (int i = 0; i < K; ++i) red[w * K + i] = v[i];
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < K; ++i) v[i] = pf_op<OP>(pf_op<OP>(pf_op<OP>(red[i], red[K + i]), red[2 * K + i]), red[3 * K + i]);
+    __syncthreads();
+  }
+}
+
+template <class M, bool WAVE>
+__device__ __forceinline__ void pf_run_body(const KfParams& kp, const PfRun& o, int64_t batch, int n, int steps, double* X, double* work,
+                                            const double* __restrict__ y, const double* __restrict__ up, int64_t up_stride,
+                                            int64_t up_step, const double* __restrict__ Q, int64_t q_stride,
+                                            const double* __restrict__ R, int64_t r_stride, const double* __restrict__ x0,
+                                            const double* __restrict__ P0, double* __restrict__ x_out, double* __restrict__ P_out,
+                                            double* __restrict__ y_out, double* __restrict__ ess_out, int* __restrict__ index_out,
+                                            double* __restrict__ Xp_out, double* __restrict__ Y_out, double* __restrict__ q_out,
+                                            int* __restrict__ status, double* dyn) {
+  constexpr int NX = M::NX, NU = M::NU, NP = M::NP, NYE = M::NY > 0 ? M::NY : M::NX, NW = NX + NYE;
+  constexpr int T = WAVE ? 64 : PF_TPB, SLOTS = WAVE ? PF_TPB / 64 : 1;
+  constexpr int ZX = (NX + 1) / 2 * 2, ZY = (NYE + 1) / 2 * 2, KR = NX > NYE ? NX : NYE;
+  __shared__ double s_L[SLOTS][NX * NX];
+  __shared__ double s_red[WAVE ? 1 : 4 * (KR + 1)];
+  const int tid = WAVE ? (threadIdx.x & 63) : threadIdx.x, lane = threadIdx.x & 63, slot = WAVE ? (threadIdx.x >> 6) : 0;
+  const int64_t b = WAVE ? (int64_t)blockIdx.x * SLOTS + slot : (int64_t)blockIdx.x;
+  if (b >= batch) return;            // (wave shape alone: a ragged last workgroup; no workgroup barrier is used there)
+  double* cdf = dyn + (WAVE ? slot * PF_WAVE_N : 0);
+  double* L = s_L[slot];
+  const unsigned bg = (unsigned)b + o.filter0;
+  X += b * n * NX;
+  work += b * n * NW;
+  Q += b * q_stride;
+  R += b * r_stride;
+  if (P0) {                          // the initial sample x0 + L_P0 z (pf.py:168-188), step number 0 of stream 0
+    if (tid == 0) pf_cholesky(NX, P0 + b * NX * NX, L);
+    pf_sync<WAVE>();
+    for (int j = tid; j < n; j += T) {
+      double z[ZX];
+      pf_normals(o, (unsigned)j, 0u, bg, 0u, z);
+#pragma unroll
+      for (int i = 0; i < NX; ++i) {
+        double s = x0[b * NX + i];
+#pragma unroll
+        for (int k = 0; k <= i; ++k) s += L[i * NX + k] * z[k];
+        X[(int64_t)j * NX + i] = s;
+      }
+    }
+    pf_sync<WAVE>();
+  }
+  if (tid == 0) pf_cholesky(NX, Q, L);
+  pf_sync<WAVE>();
+  double sig[NYE];
+#pragma unroll
+  for (int a = 0; a < NYE; ++a) sig[a] = ::sqrt(R[a * NYE + a]);
+  const double rough = (o.flags & PF_ROUGHENING) ? o.K * ::pow((double)n, -1.0 / NX) : 0.0;
+  const int chunk = (n + T - 1) / T, clo = tid * chunk < n ? tid * chunk : n, chi = clo + chunk < n ? clo + chunk : n;
+  for (int st = 0; st < steps; ++st) {
+    const unsigned k = o.step0 + (unsigned)st;
+    const bool last_step = st == steps - 1;
+    const int64_t row = (int64_t)st * batch + b;
+    const double* upk = up + st * up_step + b * up_stride;
+    double u[MaxOne<NU>::v], p[MaxOne<NP>::v], ym[NYE];
+#pragma unroll
+    for (int i = 0; i < NU; ++i) u[i] = upk[i];
+#pragma unroll
+    for (int i = 0; i < NP; ++i) p[i] = upk[NU + i];
+#pragma unroll
+    for (int a = 0; a < NYE; ++a) ym[a] = y[row * NYE + a];
+    // 1. propagate, add the process noise, measure, add the measurement noise; the log-likelihood goes to LDS
+    double mx[1] = {-INFINITY};
+    for (int j = tid; j < n; j += T) {
+      double xs[NX], xo[NX], yy[NYE], z[ZX], zv[ZY];
+#pragma unroll
+      for (int i = 0; i < NX; ++i) xs[i] = X[(int64_t)j * NX + i];
+      if (kp.continuous && !M::DISCRETE)
+        model_step<M>(4, kp.n_sub, xs, u, p, kp.dt, xo);
+      else
+        model_step<M>(kp.erk_order, kp.n_sub, xs, u, p, kp.dt, xo);
+      pf_normals(o, (unsigned)j, k, bg, 1u, z);
+#pragma unroll
+      for (int i = 0; i < NX; ++i) {
+        double w = 0.0;
+#pragma unroll
+        for (int c = 0; c <= i; ++c) w += L[i * NX + c] * z[c];
+        xo[i] += w;
+        work[(int64_t)j * NW + i] = xo[i];
+        if (last_step && Xp_out) Xp_out[(b * n + j) * NX + i] = xo[i];
+      }
+      if constexpr (M::NY > 0) {
+        M::meas(xo, u, p, kp.dt, yy);
+      } else {
+#pragma unroll
+        for (int a = 0; a < NYE; ++a) yy[a] = xo[a];
+      }
+      pf_normals(o, (unsigned)j, k, bg, 2u, zv);
+      double l = 0.0;
+#pragma unroll
+      for (int a = 0; a < NYE; ++a) {
+        yy[a] += sig[a] * zv[a];
+        work[(int64_t)j * NW + NX + a] = yy[a];
+        if (last_step && Y_out) Y_out[(b * n + j) * NYE + a] = yy[a];
+        const double e = (yy[a] - ym[a]) / sig[a];
+        l -= 0.5 * (e * e);
+      }
+      cdf[j] = l;
+      mx[0] = ::fmax(mx[0], l == l ? l : INFINITY);      // a NaN must not hide behind fmax
+    }
+    // 2. weights relative to the largest one, effective sample size
+    pf_reduce<WAVE, 2>(mx, s_red);
+    const bool fine = mx[0] > -INFINITY && mx[0] < INFINITY;
+    double ess = __builtin_nan("");
+    if (fine) {
+      double ss[2] = {0.0, 0.0};
+      for (int j = tid; j < n; j += T) {
+        const double e = ::exp(cdf[j] - mx[0]);
+        cdf[j] = e;
+        ss[0] += e;
+        ss[1] += e * e;
+      }
+      pf_reduce<WAVE, 0>(ss, s_red);
+      ess = ss[0] * ss[0] / ss[1];
+      for (int j = tid; j < n; j += T) {
+        const double q = cdf[j] / ss[0];
+        cdf[j] = q;
+        if (last_step && q_out) q_out[b * n + j] = q;
+      }
+      pf_sync<WAVE>();
+      // 3. inclusive scan: running sums inside a lane's chunk, the chunk totals across lanes with __shfl_up, the waves through LDS
+      double s = 0.0;
+      for (int j = clo; j < chi; ++j) { s += cdf[j]; cdf[j] = s; }
+      double inc = s;
+#pragma unroll
+      for (int d = 1; d < 64; d <<= 1) {
+        const double t = __shfl_up(inc, d);
+        if (lane >= d) inc += t;
+      }
+      double off = inc - s;            // what the lanes in front of this one in its wave hold
+      if constexpr (!WAVE) {
+        const int w = threadIdx.x >> 6;
+        if (lane == 63) s_red[w] = inc;
+        __syncthreads();
+        double pre = 0.0;
+        for (int v = 0; v < w; ++v) pre += s_red[v];
+        off += pre;
+      }
+      for (int j = clo; j < chi; ++j) cdf[j] += off;
+    } else {
+      if (tid == 0 && status[b * 2] == 0) { status[b * 2] = PF_STATUS_NOT_FINITE; status[b * 2 + 1] = (int)k; }
+      if (last_step && q_out)
+        for (int j = tid; j < n; j += T) q_out[b * n + j] = __builtin_nan("");
+    }
+    pf_sync<WAVE>();
+    if (tid == 0) ess_out[row] = ess;
+    // 4. resampling (numpy's `choice`: first index whose cdf exceeds u cdf[-1]) and the gather into the particle array
+    double usys = 0.0;
+    if (o.flags & PF_SYSTEMATIC) {
+      const Philox4 r = philox4x32_10(0u, k, bg, 3u << 16, o.key0, o.key1);
+      usys = pf_uniform(r.r0, r.r1);
+    }
+    const double last = fine ? cdf[n - 1] : 0.0;
+    double lo[NX], hi[NX], ys[KR];
+#pragma unroll
+    for (int i = 0; i < NX; ++i) { lo[i] = INFINITY; hi[i] = -INFINITY; }
+#pragma unroll
+    for (int a = 0; a < KR; ++a) ys[a] = 0.0;
+    for (int j = tid; j < n; j += T) {
+      int i = j;
+      if (fine) {
+        double uj;
+        if (o.flags & PF_SYSTEMATIC) {
+          uj = ((double)j + usys) / (double)n;
+        } else {
+          const Philox4 r = philox4x32_10((unsigned)j, k, bg, 3u << 16, o.key0, o.key1);
+          uj = pf_uniform(r.r0, r.r1);
+        }
+        uj *= last;
+        int a = 0, c = n;
+        while (a < c) {
+          const int m = (a + c) >> 1;
+          if (cdf[m] > uj) c = m; else a = m + 1;
+        }
+        i = a < n ? a : n - 1;
+      }
+      if (index_out) index_out[row * n + j] = i;
+#pragma unroll
+      for (int c = 0; c < NX; ++c) {
+        const double x = work[(int64_t)i * NW + c];
+        X[(int64_t)j * NX + c] = x;
+        lo[c] = ::fmin(lo[c], x);
+        hi[c] = ::fmax(hi[c], x);
+      }
+#pragma unroll
+      for (int a = 0; a < NYE; ++a) ys[a] += work[(int64_t)i * NW + NX + a];
+    }
+    // 5. roughening (pf.py:409-415): noise of variance K (max - min) N^(-1/nx) per state
+    double sd[NX];
+    if (o.flags & PF_ROUGHENING) {
+      pf_reduce<WAVE, 1>(lo, s_red);
+      pf_reduce<WAVE, 2>(hi, s_red);
+#pragma unroll
+      for (int i = 0; i < NX; ++i) sd[i] = ::sqrt(rough * (hi[i] - lo[i]));
+    }
+    // 6. mean, covariance (unbiased, two passes like np.cov), mean of the resampled measurements; every lane re-reads its own rows
+    double xsum[KR];
+#pragma unroll
+    for (int i = 0; i < KR; ++i) xsum[i] = 0.0;
+    for (int j = tid; j < n; j += T) {
+      double z[ZX];
+      if (o.flags & PF_ROUGHENING) pf_normals(o, (unsigned)j, k, bg, 4u, z);
+#pragma unroll
+      for (int i = 0; i < NX; ++i) {
+        double x = X[(int64_t)j * NX + i];
+        if (o.flags & PF_ROUGHENING) {
+          x += sd[i] * z[i];
+          X[(int64_t)j * NX + i] = x;
+        }
+        xsum[i] += x;
+      }
+    }
+    pf_reduce<WAVE, 0>(xsum, s_red);
+    pf_reduce<WAVE, 0>(ys, s_red);
+    double mean[NX];
+#pragma unroll
+    for (int i = 0; i < NX; ++i) {
+      mean[i] = xsum[i] / n;
+      if (tid == 0) x_out[row * NX + i] = mean[i];
+    }
+    if (tid == 0)
+#pragma unroll
+      for (int a = 0; a < NYE; ++a) y_out[row * NYE + a] = ys[a] / n;
+#pragma unroll
+    for (int i = 0; i < NX; ++i) {
+      double cs[KR];
+#pragma unroll
+      for (int c = 0; c < KR; ++c) cs[c] = 0.0;
+      for (int j = tid; j < n; j += T) {
+        const double di = X[(int64_t)j * NX + i] - mean[i];
+#pragma unroll
+        for (int c = 0; c <= i; ++c) cs[c] += di * (X[(int64_t)j * NX + c] - mean[c]);
+      }
+      pf_reduce<WAVE, 0>(cs, s_red);
+      if (tid == 0)
+#pragma unroll
+        for (int c = 0; c <= i; ++c) {
+          const double v = cs[c] / (n - 1);
+          P_out[(row * NX + i) * NX + c] = v;
+          P_out[(row * NX + c) * NX + i] = v;
+        }
+    }
+    pf_sync<WAVE>();       // the next step overwrites the propagated particles and the cdf that this step's search read
+  }
+}
+
+template <class M>
+__global__ __launch_bounds__(PF_TPB) void pf_run_kernel(KfParams kp, PfRun o, int64_t batch, int n, int steps, double* X, double* work,
+                                                        const double* __restrict__ y, const double* __restrict__ up,
+                                                        int64_t up_stride, int64_t up_step, const double* __restrict__ Q,
+                                                        int64_t q_stride, const double* __restrict__ R, int64_t r_stride,
+                                                        const double* __restrict__ x0, const double* __restrict__ P0,
+                                                        double* __restrict__ x_out, double* __restrict__ P_out,
+                                                        double* __restrict__ y_out, double* __restrict__ ess_out,
+                                                        int* __restrict__ index_out, double* __restrict__ Xp_out,
+                                                        double* __restrict__ Y_out, double* __restrict__ q_out,
+                                                        int* __restrict__ status) {
+  extern __shared__ double pf_dyn[];   // the cdf: n doubles, or 64 for each of the four one-wave filters
+  if (n <= PF_WAVE_N)
+    pf_run_body<M, true>(kp, o, batch, n, steps, X, work, y, up, up_stride, up_step, Q, q_stride, R, r_stride, x0, P0, x_out, P_out, y_out,
+                         ess_out, index_out, Xp_out, Y_out, q_out, status, pf_dyn);
+  else
+    pf_run_body<M, false>(kp, o, batch, n, steps, X, work, y, up, up_stride, up_step, Q, q_stride, R, r_stride, x0, P0, x_out, P_out, y_out,
+                          ess_out, index_out, Xp_out, Y_out, q_out, status, pf_dyn);
+}
+
 }  // namespace hilo

@@ -8,6 +8,10 @@ split here: the function, the resampling gather and the statistics of the partic
 generator in the reference's order - process noise from the sampling function (`pdf`, default `lhsnorm`), measurement noise
 `sqrt(R) @ randn`, the uniforms `np.random.choice` draws for the resampling, the roughening noise - so a seeded run consumes the
 stream exactly like the reference (for a batch: filter after filter inside each of these stages).
+
+`generator='device'` is the batched form of the same flow: every draw comes from a counter-based generator on the device
+(Philox4x32-10 on (particle, step, filter, purpose), include/hilo_hip.h::hilo_pf_run), a whole run of `steps` steps is ONE launch,
+and nothing goes through the host.  Its sampler is the plain correlated normal, not `lhsnorm`.
 """
 import warnings
 
@@ -41,7 +45,33 @@ class ParticleFilter(_KalmanFilter):
     _type = 'particle filter'
 
     def __init__(self, model, id=None, name=None, plot_backend=None, variant=None, roughening=False, prior_editing=False,
-                 device_index=None, **kwargs):
+                 device_index=None, generator='numpy', seed=0, resampling='multinomial', filter_offset=0, **kwargs):
+        """generator='numpy' (default): the reference's flow, random numbers from numpy's global generator in its order.
+        generator='device': random numbers drawn on the device, `estimate(..., steps=k)` runs k steps in one launch.  The initial
+        particles, the process and the roughening noise are PLAIN correlated normal samples (x0 + L z with the Cholesky factor L) -
+        not the Latin-hypercube sampler `lhsnorm` of the default mode, and no user sampler.  seed: key of the generator;
+        resampling: 'multinomial' (numpy's `choice`) or 'systematic'; filter_offset: global number of this batch's first filter
+        (a shard of a larger batch draws what it would have drawn inside the whole batch)."""
+        if generator not in ('numpy', 'device'):
+            raise ValueError(f"generator='{generator}' is not available. Use 'numpy' (the reference's host-side draws) or 'device' "
+                             f"(draws on the device, several steps per launch).")
+        if resampling not in ('multinomial', 'systematic'):
+            raise ValueError(f"resampling='{resampling}' is not available. Use 'multinomial' or 'systematic'.")
+        if generator == 'numpy' and (resampling != 'multinomial' or int(seed) != 0 or int(filter_offset) != 0):
+            raise ValueError("resampling=, seed= and filter_offset= belong to generator='device'. With generator='numpy' the filter "
+                             "resamples like np.random.choice and is seeded through np.random.seed; pass generator='device' to use them.")
+        if generator == 'device':
+            if prior_editing:
+                raise NotImplementedError("prior_editing=True is not available with generator='device' (its loop redraws on the host "
+                                          "until every particle is plausible). Use generator='numpy' for prior editing, or "
+                                          "roughening=True with generator='device'.")
+            if not 0 <= int(seed) < 2 ** 64 or not 0 <= int(filter_offset) < 2 ** 32:
+                raise ValueError("seed must lie in 0..2^64-1 and filter_offset in 0..2^32-1: they are words of the generator's key "
+                                 "and counter.")
+        self._generator, self._seed, self._resampling, self._filter_offset = generator, int(seed), resampling, int(filter_offset)
+        self._step = 0
+        self._fresh = True
+        self.status = None
         if model.is_linear():
             warnings.warn("The supplied model is linear. For better efficiency use an observer targeted at the "
                           "estimation of linear systems.")
@@ -98,6 +128,9 @@ class ParticleFilter(_KalmanFilter):
         particles as columns; anything else is probed with one draw (same decisions and messages as pf.py:197-249)."""
         if not callable(pdf):
             raise ValueError(f"Probability density function of the {self.type} needs to be callable.")
+        if self._generator == 'device':
+            raise NotImplementedError("generator='device' draws plain correlated normal samples on the device and cannot call a "
+                                      "Python sampler. Use generator='numpy' with a probability_density_function of your own.")
         notes = dict(getattr(pdf, '__annotations__', None) or {})
         if len(notes) == len(self._SAMPLER_SIGNATURE) and 'return' in notes:
             for found, (want, what) in zip(notes.values(), self._SAMPLER_SIGNATURE):
@@ -134,6 +167,9 @@ class ParticleFilter(_KalmanFilter):
             self._sample_size = n_s
         if not 2 <= int(self._sample_size) <= 8192:
             raise ValueError("the particle filter is built for 2 to 8192 particles per filter")
+        if self._generator == 'device' and self._model.n_x > 16:
+            raise NotImplementedError(f"generator='device' is built for up to 16 states, the model has {self._model.n_x}. Use "
+                                      f"generator='numpy', whose noise is drawn on the host.")
         super().setup()
         m = self._model
         if m.n_y == 0:
@@ -142,6 +178,7 @@ class ParticleFilter(_KalmanFilter):
         self._n_ye = m.n_y if m.n_y else m.n_x
         self._R = torch.zeros(self._n_ye, self._n_ye, dtype=torch.float64, device=self._dev)     # pf.py:337-338
         self._X = None
+        self._step, self._fresh, self.status = 0, True, None
 
     @_KalmanFilter.R.setter
     def R(self, v):
@@ -201,6 +238,96 @@ class ParticleFilter(_KalmanFilter):
                                             stream_ptr(dev)))
         return xm, ym, P, lo, hi
 
+    # ---- generator='device': whole runs in one launch (hilo_pf_run) -------------------------------------------------------------
+    def set_initial_guess(self, x0, P0=None):
+        super().set_initial_guess(x0, P0=P0)
+        if self._generator == 'device':        # new particles are drawn in the next launch, and the step counter starts again
+            self._X, self._step, self._fresh, self.status = None, 0, True, None
+
+    def _estimate_device(self, y, u, p, steps, return_index):
+        """`steps` steps in ONE launch with the conventions of `_KalmanFilter._estimate_steps`: y [steps, B, n_y]; u [steps, B, n_u]
+        or [B, n_u] (held); p like a single step; a single row of u / p / Q / R is shared by the batch (stride 0).  Without
+        `steps=` one step, and the solution is shaped like the numpy mode's."""
+        single = steps is None
+        steps = 1 if single else int(steps)
+        if steps < 1:
+            raise ValueError(f"steps={steps}: at least one step per call")
+        N, nx, ny, dev = int(self._sample_size), self._n_x, self._n_ye, self._dev
+        nu, n_p = self._n_u, self._n_p
+        yt = to_dev(y, dev)
+        B = self._x.shape[0]
+        if yt.numel() % (steps * ny):
+            raise ValueError(f"Dimension mismatch for variable y. Supplied dimension is {yt.numel()}, but required dimension "
+                             f"is a multiple of {steps * ny}.")
+        yt = yt.reshape(steps, -1, ny).contiguous()
+        if yt.shape[1] != B:
+            if B != 1 or not self._fresh:
+                raise ValueError(f"Dimension mismatch. Supplied {yt.shape[1]} measurement vectors per step for {B} filters.")
+            B = yt.shape[1]
+            self._x = self._x.expand(B, -1).contiguous()
+            self._P = self._P.expand(B, -1, -1).contiguous()
+        ut = pt = None
+        if n_p:
+            pt = self._p if p is None else to_dev(p, dev)
+            if pt is None:
+                raise RuntimeError("No parameter values supplied. Please run set_initial_parameter_values() or pass p=.")
+            pt = pt.reshape(1, -1, n_p)
+            if pt.shape[1] not in (1, B):
+                raise ValueError(f"Dimension mismatch for variable p: {pt.shape[1]} parameter vectors for {B} filters.")
+        if nu:
+            if u is None:
+                raise RuntimeError("No input data supplied.")
+            ut = to_dev(u, dev)
+            if ut.numel() == steps * B * nu and steps > 1:
+                ut = ut.reshape(steps, B, nu)
+            else:
+                ut = ut.reshape(1, -1, nu)
+                if ut.shape[1] not in (1, B):
+                    raise ValueError(f"Dimension mismatch for variable u: {ut.shape[1]} input vectors for {B} filters.")
+        # [u; p] rows as hilo_pf_run reads them: up + k up_step + b up_stride (one row shared by the batch / held over the steps: 0)
+        upt, us, ustep = None, 0, 0
+        parts = [t for t in (ut, pt) if t is not None]
+        if parts:
+            S, Bc = max(t.shape[0] for t in parts), max(t.shape[1] for t in parts)
+            upt = torch.cat([t.expand(S, Bc, -1) for t in parts], dim=2).contiguous()
+            us = (nu + n_p) if Bc > 1 else 0
+            ustep = Bc * (nu + n_p) if S > 1 else 0
+        Q, R = self._Q.contiguous(), self._R.contiguous()
+        qs, rs = self._cov_stride(Q, B), self._cov_stride(R, B)
+        x0 = P0 = None
+        if self._fresh:
+            x0, P0 = self._x.expand(B, -1).contiguous(), self._P.expand(B, -1, -1).contiguous()
+            self._X = torch.empty(B, N, nx, dtype=torch.float64, device=dev)
+            self._work = torch.empty(B, N, nx + ny, dtype=torch.float64, device=dev)
+            self.status = torch.zeros(B, 2, dtype=torch.int32, device=dev)
+        f64 = dict(dtype=torch.float64, device=dev)
+        xo, Po, yo = torch.empty(steps, B, nx, **f64), torch.empty(steps, B, nx, nx, **f64), torch.empty(steps, B, ny, **f64)
+        ess = torch.empty(steps, B, **f64)
+        Xp, Y, q = torch.empty(B, N, nx, **f64), torch.empty(B, N, ny, **f64), torch.empty(B, N, **f64)
+        ind = torch.empty(steps, B, N, dtype=torch.int32, device=dev) if return_index else None
+        opts = _lib.PfOpts(seed=self._seed, step0=self._step, filter_offset=self._filter_offset,
+                           flags=(1 if self._resampling == 'systematic' else 0) | (2 if self._roughening else 0),
+                           K=float(self._roughening_tuning_param) if self._roughening else 0.)
+        import ctypes as C
+        _lib.check(_lib.lib().hilo_pf_run(self._handle, C.byref(opts), B, N, steps, ptr(self._X), ptr(self._work), ptr(yt), ptr(upt), us,
+                                          ustep, ptr(Q), qs, ptr(R), rs, ptr(x0), ptr(P0), ptr(xo), ptr(Po), ptr(yo), ptr(ess), ptr(ind),
+                                          ptr(Xp), ptr(Y), ptr(q), ptr(self.status), stream_ptr(dev)))
+        self._fresh = False
+        self._step += steps
+        self._x, self._P = xo[-1], Po[-1]
+        self._last = dict(X_prop=Xp, Y=Y, q=q)
+        if return_index:
+            self._last['index'] = ind
+        host = not isinstance(y, torch.Tensor)
+        cv = (lambda t: t.cpu().numpy()) if host else (lambda t: t)
+        if single:
+            xs = cv(xo[0])
+            self.solution._set(x=xs.T if (host and B == 1) else xs, X=cv(self._X.transpose(1, 2)), P=cv(Po[0]), y=cv(yo[0]),
+                               ess=cv(ess[0]))
+        else:
+            self.solution._set(x=cv(xo), X=cv(self._X.transpose(1, 2)), P=cv(Po), y=cv(yo), ess=cv(ess))
+        return self.solution
+
     # ---- estimate (pf.py:340-422) --------------------------------------------------------------------------------------------
     def estimate(self, y=None, u=None, p=None, **kwargs):
         self._check_setup()
@@ -209,6 +336,8 @@ class ParticleFilter(_KalmanFilter):
                                "the particle filter!")
         if y is None:
             raise RuntimeError("No measurement data supplied.")
+        if self._generator == 'device':
+            return self._estimate_device(y, u, p, kwargs.get('steps'), bool(kwargs.get('return_index', False)))
         N, nx, ny, dev = int(self._sample_size), self._n_x, self._n_ye, self._dev
         yt = to_dev(y, dev).reshape(-1, ny)
         B = yt.shape[0]

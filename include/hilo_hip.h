@@ -133,6 +133,45 @@ int hilo_pf_resample(hilo_kf* kf, int64_t batch, int n_samples, const double* X_
    the particles first: the roughening step `X += dx` (pf.py:415). */
 int hilo_pf_stats(hilo_kf* kf, int64_t batch, int n_samples, double* X, const double* Y, const double* add,
                   double* x_mean, double* y_mean, double* P, double* x_min, double* x_max, void* stream);
+/* The whole of `ParticleFilter.estimate` (pf.py:340-422) for `steps` steps of a batch of filters in ONE launch, every random number
+   drawn on the device (the reference draws with numpy on the host, pf.py:364-368, :404-415, and stops at steps > 1, pf.py:360).
+   A draw is a pure function of (seed, filter, absolute step, particle, purpose): Philox4x32-10 with key (seed low, seed high) on the
+   counter (j, k, b + filter_offset, stream << 16 | d) - j the particle, k = step0 + the step within the call, b the filter, d the
+   block; streams 0 initial sample (k = 0), 1 process noise, 2 measurement noise, 3 resampling, 4 roughening.  One output
+   (r0, r1, r2, r3) gives u1 = (((r0 >> 5) << 26 | r1 >> 6) + 0.5) 2^-53 and u2 likewise from (r2, r3); normals 2d and 2d+1 of a
+   vector are sqrt(-2 ln u1) cos(2 pi u2) and sqrt(-2 ln u1) sin(2 pi u2) of block d.  Per step:
+     X_prop = Phi(X, u, p) + L_Q z (pf.py:140-146; L_Q the lower Cholesky factor of Q, a non-positive pivot zeroes its column)
+     Y = h(X_prop, u, p) + sqrt(diag R) z (pf.py:131-138)
+     q_j proportional to exp(l_j - max l), l_j the log-likelihood of particle j (pf.py:148-166 up to rounding wherever the
+       reference's weights are finite); ess = 1 / sum q_j^2
+     resampling (pf.py:404-407): numpy's `choice` on u1 of block 0 per particle, or with HILO_PF_SYSTEMATIC u_j = (j + u) / N from
+       the one uniform of particle 0
+     HILO_PF_ROUGHENING (pf.py:409-415): particle j gains sqrt(K (max_i - min_i) N^(-1/nx)) z_i in state i
+     x = mean, P = np.cov, y = mean of the resampled measurements (pf.py:418-420)
+   X [B][n_samples][nx] in and out (particle-major); P0 not NULL: X is drawn first as x0 [B][nx] + L_P0 z, P0 [B][nx][nx]
+   (pf.py:168-188).  work [B][n_samples][nx + ny]: scratch (the propagated particles and their measurements).  y [steps][B][ny];
+   [u; p] of step k and filter b at up + k up_step + b up_stride (0: held / shared); Q, R as for hilo_pf_function.
+   x_out [steps][B][nx], P_out [steps][B][nx][nx], y_out [steps][B][ny], ess_out [steps][B]; index_out [steps][B][n_samples] or
+   NULL; X_prop_out, Y_out, q_out: the last step's intermediates, each may be NULL.  status [B][2] (code, step): written once, when
+   a filter's code still is 0 - HILO_PF_STATUS_NOT_FINITE: the weights of that step were not finite (NaN measurement or state, or
+   every particle infinitely far); the step then leaves the propagated particles unresampled (index = identity) and the run goes
+   on.  n_samples 2..8192 (up to 64: one wave per filter, four filters per workgroup; above: one workgroup per filter), nx <= 16. */
+#define HILO_PF_SYSTEMATIC 1
+#define HILO_PF_ROUGHENING 2
+#define HILO_PF_STATUS_NOT_FINITE 1
+typedef struct hilo_pf_opts {
+  uint64_t seed;
+  int64_t step0;          /* absolute number of the first step of this call */
+  int64_t filter_offset;  /* global number of filter 0 of this batch */
+  int32_t flags;          /* HILO_PF_* */
+  int32_t reserved;
+  double K;               /* read with HILO_PF_ROUGHENING */
+} hilo_pf_opts;
+int hilo_pf_run(hilo_kf* kf, const hilo_pf_opts* opts, int64_t batch, int n_samples, int steps, double* X, double* work,
+                const double* y, const double* up, int64_t up_stride, int64_t up_step, const double* Q, int64_t q_stride,
+                const double* R, int64_t r_stride, const double* x0, const double* P0, double* x_out, double* P_out,
+                double* y_out, double* ess_out, int32_t* index_out, double* X_prop_out, double* Y_out, double* q_out,
+                int32_t* status, void* stream);
 /* widths of the packed tiles: xp = nx+1 ([x|P]); pred = nx+1 (KF/EKF) or 1+nx+(2nx+1) (UKF [x|P|X]) */
 int hilo_kf_dims(const hilo_kf* kf, int* nx, int* nu, int* np, int* ny, int* pred_width);
 
