@@ -33,10 +33,11 @@ from .control_loop import SimpleControlLoop
 from .pf import ParticleFilter
 from .lqr import LinearQuadraticRegulator, LQR
 from .pid import PID
+from .data import DataGenerator, DataSet
 
 from .ann import ArtificialNeuralNetwork, ANN, Layer, Dense, Dropout
 
 PF = ParticleFilter
 
 __all__ += ['NMPC', 'SMPC', 'MovingHorizonEstimator', 'MHE', 'LMPC', 'expr', 'SimpleControlLoop', 'ParticleFilter', 'PF',
-            'LinearQuadraticRegulator', 'LQR', 'PID', 'ArtificialNeuralNetwork', 'ANN', 'Layer', 'Dense', 'Dropout']
+            'LinearQuadraticRegulator', 'LQR', 'PID', 'DataGenerator', 'DataSet', 'ArtificialNeuralNetwork', 'ANN', 'Layer', 'Dense', 'Dropout']

@@ -7,7 +7,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libhilo_hip.so')
-SOURCES = ['hilo_api.hip', 'hilo_kf.hip', 'hilo_sim.hip', 'hilo_pid.hip', 'hilo_lqr.hip', 'hilo_gp.hip', 'hilo_ann.hip', 'hilo_nmpc.hip', 'hilo_qp.hip', 'hilo_mhe.hip',
+SOURCES = ['hilo_api.hip', 'hilo_kf.hip', 'hilo_sim.hip', 'hilo_pid.hip', 'hilo_datagen.hip', 'hilo_lqr.hip', 'hilo_gp.hip', 'hilo_ann.hip', 'hilo_nmpc.hip', 'hilo_qp.hip', 'hilo_mhe.hip',
            'hilo_nmpc_gen_chemostat4.hip', 'hilo_nmpc_gen_robot6.hip', 'hilo_nmpc_coll.hip', 'hilo_nmpc_tv.hip', 'hilo_mhe_est.hip', 'hilo_nmpc_long.hip', 'hilo_jit.hip', 'hilo_nmpc_user.hip',
            'hilo_selftest.hip']
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-fno-gpu-rdc', '-Wno-unused-result'] + \

@@ -41,6 +41,13 @@ class PidOpts(C.Structure):
                 ('out_index', C.c_int32 * 4), ('lo', C.c_double * 4), ('hi', C.c_double * 4)]
 
 
+class DatagenOpts(C.Structure):
+    """hilo_datagen_opts: kind 0 = staircase uniform, 1 = staircase normal, 2 = chirp; noise_kind 0 = none, 1 = uniform, 2 = normal."""
+    _fields_ = [('seed', C.c_uint64), ('instance_offset', C.c_int64), ('kind', C.c_int32), ('hold', C.c_int32), ('shift', C.c_int32),
+                ('difference', C.c_int32), ('skip_mask', C.c_int32), ('reserved', C.c_int32), ('a', C.c_double * 4), ('b', C.c_double * 4),
+                ('noise_kind', C.c_int32 * 12), ('noise_seed', C.c_uint64 * 12), ('na', C.c_double * 12), ('nb', C.c_double * 12)]
+
+
 class PfOpts(C.Structure):
     """hilo_pf_opts: flags 1 = systematic resampling, 2 = roughening (K)."""
     _fields_ = [('seed', C.c_uint64), ('step0', C.c_int64), ('filter_offset', C.c_int64), ('flags', C.c_int32),
@@ -124,6 +131,7 @@ def _declare(lib):
         'hilo_pid_call': (C.c_int, [P(PidOpts), i64, dbl, vp, vp, i64, vp, i64, vp, vp, vp]),
         'hilo_pid_loop': (C.c_int, [vp, P(SimOpts), P(PidOpts), i64, i32, vp, vp, i64, vp, i64, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp,
                                     vp, vp]),
+        'hilo_datagen_run': (C.c_int, [vp, P(SimOpts), P(DatagenOpts), vp, i64, i32, vp, vp, i64, vp, vp, vp, vp, vp, vp]),
         'hilo_model_linearize': (C.c_int, [vp, i64, vp, vp, i64, vp, vp, vp, vp]),
         'hilo_lqr_gain': (C.c_int, [i32, i32, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, P(LqrOpts), vp, vp, vp, vp]),
         'hilo_lqr_call': (C.c_int, [vp, P(LqrOpts), i64, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]),

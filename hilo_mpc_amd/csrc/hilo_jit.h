@@ -62,6 +62,8 @@ struct JitKfKernels {
   int rollout_scratch = 0;                       // bytes of scratch per lane of that kernel (0: everything in registers)
   hipFunction_t pid_loop = nullptr;              // the roll-out with a PID law computing the input each interval (hilo_pid.h::pid_loop_body)
   int pid_loop_scratch = 0;                      // bytes of scratch per lane of that kernel
+  hipFunction_t datagen = nullptr;               // the roll-out with the excitation signal and the data set (hilo_datagen.h::datagen_body)
+  int datagen_scratch = 0;                       // bytes of scratch per lane of that kernel
   hipFunction_t rollout_bdf = nullptr;           // the same with the implicit method (hilo_integrate.h::rollout_bdf_body, SIM_BDF)
   int rollout_bdf_scratch = 0;                   // bytes of scratch per lane of that kernel
   hipFunction_t rollout_idas = nullptr;          // a model with algebraic states in [x; z] (hilo_integrate.h::rollout_idas_body, SIM_IDAS);

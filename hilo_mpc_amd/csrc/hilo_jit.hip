@@ -372,7 +372,7 @@ int jit_kf_kernels(const std::string& user_source, int device, JitKfKernels* out
                   "unscented filter's prediction tiles, 64 x n_x (3 n_x + 2) doubles, pass the 160 KB of LDS at n_x = 10 - the model has %d",
                   KF_MAX_NX, nx);
   }
-  std::string tu = "#define HILO_TRIG_CALLS 1\n#include \"hilo_kf_kernel.h\"\n#include \"hilo_integrate.h\"\n#include \"hilo_pid.h\"\n#include \"hilo_lqr.h\"\nextern \"C\" { __device__ const double* hilo_user_gp[4]; }\nnamespace hilo {\n";
+  std::string tu = "#define HILO_TRIG_CALLS 1\n#include \"hilo_kf_kernel.h\"\n#include \"hilo_integrate.h\"\n#include \"hilo_pid.h\"\n#include \"hilo_datagen.h\"\n#include \"hilo_lqr.h\"\nextern \"C\" { __device__ const double* hilo_user_gp[4]; }\nnamespace hilo {\n";
   tu += user_source;
   tu += R"(
 }  // namespace hilo
@@ -470,6 +470,16 @@ extern "C" __global__ __launch_bounds__(ROLLOUT_TPB) void hilo_user_pid_loop(KfP
     pid_loop_body<UserModel>(kp, sp, po, batch, steps, x0, up, up_stride, spt, sp_stride, sp_step, gains, gain_stride, mem, X, U, Y, J,
                              x_final, stats, t0, hc);
 }
+extern "C" __global__ __launch_bounds__(ROLLOUT_TPB) void hilo_user_datagen(KfParams kp, SimParams sp, DatagenParams dg,
+                                                                            const double* __restrict__ chirp, int64_t batch, int T,
+                                                                            const double* __restrict__ x0,
+                                                                            const double* __restrict__ up, int64_t up_stride,
+                                                                            double* __restrict__ F, double* __restrict__ L,
+                                                                            double* __restrict__ X, double* __restrict__ U,
+                                                                            int* __restrict__ stats, double t0) {
+  if constexpr (UserModel::NU > 0 && UserModel::NU <= DG_MAX_NU && UserModel::NX <= DG_MAX_NX && model_nz<UserModel>::value == 0)
+    datagen_body<UserModel>(kp, sp, dg, chirp, batch, T, x0, up, up_stride, F, L, X, U, stats, t0);
+}
 extern "C" __global__ __launch_bounds__(ROLLOUT_TPB) void hilo_user_rollout_bdf(KfParams kp, SimParams sp, int64_t batch, int steps,
                                                                                 const double* __restrict__ x0,
                                                                                 const double* __restrict__ up, int64_t up_stride,
@@ -558,6 +568,8 @@ extern "C" __global__ void hilo_user_kf_info(int* o) {
   if (hipFuncGetAttribute(&k.rollout_scratch, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, k.rollout) != hipSuccess) k.rollout_scratch = 0;
   HILO_HIP_CHECK(hipModuleGetFunction(&k.pid_loop, mod, "hilo_user_pid_loop"));
   if (hipFuncGetAttribute(&k.pid_loop_scratch, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, k.pid_loop) != hipSuccess) k.pid_loop_scratch = 0;
+  HILO_HIP_CHECK(hipModuleGetFunction(&k.datagen, mod, "hilo_user_datagen"));
+  if (hipFuncGetAttribute(&k.datagen_scratch, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, k.datagen) != hipSuccess) k.datagen_scratch = 0;
   HILO_HIP_CHECK(hipModuleGetFunction(&k.rollout_bdf, mod, "hilo_user_rollout_bdf"));
   if (hipFuncGetAttribute(&k.rollout_bdf_scratch, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, k.rollout_bdf) != hipSuccess) k.rollout_bdf_scratch = 0;
   HILO_HIP_CHECK(hipModuleGetFunction(&k.rollout_idas, mod, "hilo_user_rollout_idas"));

@@ -10,6 +10,7 @@
 #include "hilo_common.h"
 #include "hilo_kf_params.h"
 #include "hilo_models.h"
+#include "hilo_philox.h"
 
 namespace hilo {
 
@@ -1197,30 +1198,11 @@ constexpr int PF_SYSTEMATIC = 1, PF_ROUGHENING = 2;
 constexpr int PF_WAVE_N = 64;        // up to this many particles a filter is ONE wave, four filters per workgroup
 constexpr int PF_STATUS_NOT_FINITE = 1;
 
-struct Philox4 { unsigned r0, r1, r2, r3; };
-HD unsigned pf_mulhi(unsigned a, unsigned b) { return (unsigned)(((unsigned long long)a * b) >> 32); }
-HD Philox4 philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned h0 = pf_mulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0, h1 = pf_mulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
-    c0 = h1 ^ c1 ^ k0; c1 = l1; c2 = h0 ^ c3 ^ k1; c3 = l0;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  return Philox4{c0, c1, c2, c3};
-}
-// 53 bits of two words, centred in their cell: never 0, so the logarithm is safe (the topmost cell rounds to 1)
-HD double pf_uniform(unsigned a, unsigned b) {
-  return ((double)(((unsigned long long)(a >> 5) << 26) | (unsigned long long)(b >> 6)) + 0.5) * 0x1p-53;
-}
+// (Philox4, philox4x32_10, pf_uniform and pf_box_muller: hilo_philox.h, shared with the data generator)
 // Box-Muller: block d supplies the normals 2d and 2d+1
 __device__ __forceinline__ void pf_normal_pair(const PfRun& o, unsigned j, unsigned k, unsigned b, unsigned stream, unsigned d, double& z0,
                                                double& z1) {
-  const Philox4 r = philox4x32_10(j, k, b, stream << 16 | d, o.key0, o.key1);
-  const double rad = ::sqrt(-2.0 * ::log(pf_uniform(r.r0, r.r1)));
-  double s, c;
-  sin_cos(6.283185307179586 * pf_uniform(r.r2, r.r3), s, c);
-  z0 = rad * c;
-  z1 = rad * s;
+  pf_box_muller(philox4x32_10(j, k, b, stream << 16 | d, o.key0, o.key1), z0, z1);
 }
 template <int N>
 __device__ __forceinline__ void pf_normals(const PfRun& o, unsigned j, unsigned k, unsigned b, unsigned stream, double (&z)[N]) {

@@ -1126,6 +1126,91 @@ class Model:
             self._sim['x'].append(x), self._sim['y'].append(y), self._sim['u'].append(u)
             self._sim['t'].append(self._sim['t'][-1] + self.dt)
 
+    def generate_data(self, signal_type, *args, output='absolute', shift=0, add_noise=None, n_samples=None, steps=None, bounds=None,
+                      mean=None, variance=None, seed=None, chirps=None, skip=None, **kwargs):
+        """dynamic_model.py:4214-4369: excite this model with a 'random_uniform' / 'random_normal' staircase or with 'chirp' signals
+        and return the `DataSet` of features and labels - for a batch of experiments (x0 [B, n_x], p0 [B, n_p] in **kwargs, which
+        go to `DataGenerator`) in ONE launch.  bounds {input: {'lb': .., 'ub': ..}} (default 0 and 1); mean / variance {input: value}
+        default to the middle of the bounds and to a third of their half width as standard deviation; chirps {input: {'type',
+        'amplitude', 'length', 'mean', 'chirp_rate', 'initial_phase', 'initial_frequency', 'initial_frequency_ratio'}}; skip: names
+        or indices of states left out.  'closed_loop' is not built."""
+        from .data import DataGenerator
+        data_generator = DataGenerator(self, **kwargs)
+        signal_type = signal_type.replace(' ', '_').lower()
+        if signal_type in ['random_uniform', 'random_normal']:
+            if n_samples is None:
+                raise ValueError(f"Generating data using the {signal_type.replace('_', ' ')} signal requires "
+                                 f"information about the number of samples by supplying the keyword 'n_samples'")
+            if steps is None:
+                raise ValueError(f"Generating data using the {signal_type.replace('_', ' ')} signal requires "
+                                 f"information about the number of steps by supplying the keyword 'steps'")
+            lbs, ubs = [], []
+            for k in self.input_names:
+                name = (bounds or {}).get(k)
+                lb = ub = None
+                if name is not None:
+                    lb = name.get('lb')
+                    if lb is None:
+                        lb = name.get('lower_bound')
+                    ub = name.get('ub')
+                    if ub is None:
+                        ub = name.get('upper_bound')
+                lbs.append(0. if lb is None else lb)
+                ubs.append(1. if ub is None else ub)
+            if signal_type == 'random_uniform':
+                data_generator.random_uniform(n_samples, steps, lbs, ubs, seed=seed)
+            else:
+                mus = [None if mean is None else mean.get(k) for k in self.input_names]
+                sigmas = [None if variance is None else variance.get(k) for k in self.input_names]
+                for k in range(self.n_u):
+                    if mus[k] is None:
+                        mus[k] = lbs[k] + (ubs[k] - lbs[k]) / 2
+                    if sigmas[k] is None:
+                        sigmas[k] = (1. / 3. * (ubs[k] - lbs[k]) / 2) ** 2  # 99.7% lie between lb and ub
+                data_generator.random_normal(n_samples, steps, mus, sigmas, seed=seed)
+        elif signal_type == 'chirp':
+            cols = [[] for _ in range(8)]
+            for k in self.input_names:
+                chirp = (chirps or {}).get(k)
+                if chirp is None:
+                    raise ValueError(f"No chirp signals supplied for input'{k}'")
+                if chirp.get('length') is None:
+                    raise ValueError(f"No length(s) supplied for input '{k}'")
+                if chirp.get('chirp_rate') is None:
+                    raise ValueError(f"No chirp rate(s) supplied for input '{k}'")
+                cols[0].append('linear' if chirp.get('type') is None else chirp.get('type'))
+                cols[1].append(1. if chirp.get('amplitude') is None else chirp.get('amplitude'))
+                cols[2].append(chirp.get('length'))
+                cols[3].append(0. if chirp.get('mean') is None else chirp.get('mean'))
+                cols[4].append(chirp.get('chirp_rate'))
+                cols[5].append(chirp.get('initial_phase'))
+                cols[6].append(chirp.get('initial_frequency'))
+                cols[7].append(chirp.get('initial_frequency_ratio'))
+            data_generator.chirp(*cols[:5], initial_phase=cols[5], initial_frequency=cols[6], initial_frequency_ratio=cols[7])
+        elif signal_type == 'closed_loop':
+            if not args:
+                raise ValueError(f"No controller supplied for {signal_type.replace('_', ' ')} setup")
+            if steps is None:
+                raise ValueError(f"Generating data using the {signal_type.replace('_', ' ')} setup requires "
+                                 f"information about the number of steps by supplying the keyword 'steps'")
+            data_generator.closed_loop(*args, steps)
+        else:
+            raise ValueError(f"Signal type '{signal_type}' not recognized. Choose 'random_uniform', 'random_normal' or 'chirp'")
+        if add_noise is not None and 'seed' not in add_noise and seed is not None:
+            add_noise = add_noise.copy()
+            add_noise['seed'] = seed
+        if skip is not None:
+            if all(isinstance(k, str) for k in skip):
+                missing = [k for k in skip if k not in self.dynamical_state_names]
+                if missing:
+                    raise ValueError(f"skip: the model has no dynamical states {missing}. Choose out of {self.dynamical_state_names}")
+                skip = [self.dynamical_state_names.index(k) for k in skip]
+            elif any(isinstance(k, str) for k in skip):
+                raise ValueError("Mixed iterables for the keyword argument 'skip' are not allowed. Either use only "
+                                 "strings or only indices (integers) in your iterable.")
+        data_generator.run(output, skip=skip, shift=shift, add_noise=add_noise)
+        return data_generator.data
+
     @property
     def solution(self):
         """`model.solution['x:f']`, `['y:f']`, `['t:f']`, `['x']` ... (the key language of base.py:2426-2470 for the last value /

@@ -361,6 +361,52 @@ int hilo_pid_loop(hilo_kf* kf, const hilo_sim_opts* sim, const hilo_pid_opts* op
                   double* h, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------- */
+/* Data generation: excitation signals, plant and data set in one launch                                   */
+/* replaces `DataGenerator.random_uniform / random_normal / chirp / run` (hilo_mpc/util/data.py:642-1167)   */
+/* ------------------------------------------------------------------------------------------------------- */
+/* One instance per lane (csrc/hilo_datagen.h::datagen_instance): per sampling interval k = 0..total_steps-1 the input vector u_k is
+   evaluated inside the kernel, the plant advanced as hilo_model_rollout advances it under an input sequence, and the states
+   scattered into features and labels in training layout.
+     kind   HILO_DATAGEN_UNIFORM  a staircase, sample s = k / hold: u_i = fma(b_i - a_i, U, a_i)            (a: lower, b: upper bound)
+            HILO_DATAGEN_NORMAL   the same with u_i = fma(sqrt(b_i), Z, a_i)                                (a: mean, b: variance)
+            HILO_DATAGEN_CHIRP    chirp_table [nu][HILO_DATAGEN_MAX_SEG][8] on the device, a segment being {type (0 linear,
+                                  1 exponential, 2 hyperbolic), point count, amplitude, mean, chirp rate, initial phase, initial
+                                  frequency, initial frequency ratio}; the local time of a segment is i dt from its start; the point
+                                  counts of every input must add up to total_steps (the host's duty)
+     draws  Philox4x32-10 on the counter (0, index, b + instance_offset, stream << 16 | d), key (seed low, seed high); block d
+            supplies values 2d and 2d+1; index = s for inputs (value i: input i), = j for the noise on state j (value i: state i,
+            key from noise_seed[i]); streams 8 / 9 input uniforms / normals, 10 / 11 noise uniforms / normals
+     noise  per state: 0 none, 1 uniform n = fma(nb - na, U, na), 2 normal n = na Z
+     F [N][B][(shift + 1) nk + nu], L [N][B][nk], N = total_steps - shift, nk the states not in skip_mask: the noisy kept state
+            xt_j = x_j + n_j goes to row j - s, block s (s = 0..shift); u_k to row k - shift, last block; the label of row
+            j - shift - 1 is xt_j, with `difference` (x_j - x_{j-1}) + (n_j - n_{j-1})
+     X [total_steps + 1][B][nx] the clean states, U [total_steps][B][nu], stats [B][4] as for hilo_model_rollout: each may be NULL
+   up: one row [u; p] per instance (up_stride 0: shared); its inputs are not read.  An instance whose integration fails gets NaN in
+   every entry made of a state it did not reach.  HILO_EINVAL for arguments out of range; HILO_ENOTSUP for HILO_SIM_BDF /
+   HILO_SIM_IDAS, a model with algebraic states, more than HILO_DATAGEN_MAX_NX states or HILO_DATAGEN_MAX_NU inputs, a model without
+   inputs, and a run-time compiled model whose kernel needs scratch memory under HILO_SIM_DOPRI5. */
+#define HILO_DATAGEN_MAX_NU 4
+#define HILO_DATAGEN_MAX_NX 12
+#define HILO_DATAGEN_MAX_SEG 8
+#define HILO_DATAGEN_UNIFORM 0
+#define HILO_DATAGEN_NORMAL 1
+#define HILO_DATAGEN_CHIRP 2
+typedef struct hilo_datagen_opts {
+  uint64_t seed;
+  int64_t instance_offset;                  /* global number of instance 0 of this batch */
+  int32_t kind, hold;                       /* HILO_DATAGEN_*; sampling intervals per sample of a staircase */
+  int32_t shift, difference;
+  int32_t skip_mask, reserved;              /* bit i: state i is left out */
+  double a[HILO_DATAGEN_MAX_NU], b[HILO_DATAGEN_MAX_NU];
+  int32_t noise_kind[HILO_DATAGEN_MAX_NX];
+  uint64_t noise_seed[HILO_DATAGEN_MAX_NX];
+  double na[HILO_DATAGEN_MAX_NX], nb[HILO_DATAGEN_MAX_NX];
+} hilo_datagen_opts;
+int hilo_datagen_run(hilo_kf* kf, const hilo_sim_opts* sim, const hilo_datagen_opts* opts, const double* chirp_table, int64_t batch,
+                     int total_steps, const double* x0, const double* up, int64_t up_stride, double* F, double* L, double* X,
+                     double* U, int32_t* stats, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------- */
 /* Linear-quadratic regulator: batched linearisation, Riccati gains and feedback                            */
 /* replaces `LinearQuadraticRegulator.setup / call` (hilo_mpc/modules/controller/lqr.py:204-306)            */
 /* ------------------------------------------------------------------------------------------------------- */
