@@ -8,7 +8,7 @@ Host classes mirror the reference API surface for the hot path only (SURVEY.md s
 """
 from .model import Model
 from .estimator import KalmanFilter, ExtendedKalmanFilter, UnscentedKalmanFilter
-from .gp import GaussianProcess, Kernel, Mean
+from .gp import GaussianProcess, GPArray, Kernel, Mean
 # the kernel and mean classes under the names of the reference's flat namespace (hilo_mpc/__init__.py:66-87)
 from .gp import (ConstantKernel, SquaredExponentialKernel, MaternKernel, ExponentialKernel, Matern32Kernel, Matern52Kernel,
                  RationalQuadraticKernel, PiecewisePolynomialKernel, DotProductKernel, PolynomialKernel, LinearKernel,
@@ -20,7 +20,7 @@ UKF = UnscentedKalmanFilter
 GP = GaussianProcess
 
 __all__ = ['Model', 'KalmanFilter', 'ExtendedKalmanFilter', 'UnscentedKalmanFilter', 'KF', 'EKF', 'UKF',
-           'GaussianProcess', 'GP', 'Kernel', 'Mean', 'ConstantKernel', 'SquaredExponentialKernel', 'MaternKernel',
+           'GaussianProcess', 'GP', 'GPArray', 'Kernel', 'Mean', 'ConstantKernel', 'SquaredExponentialKernel', 'MaternKernel',
            'ExponentialKernel', 'Matern32Kernel', 'Matern52Kernel', 'RationalQuadraticKernel', 'PiecewisePolynomialKernel',
            'DotProductKernel', 'PolynomialKernel', 'LinearKernel', 'NeuralNetworkKernel', 'PeriodicKernel', 'ConstantMean',
            'ZeroMean', 'OneMean', 'PolynomialMean', 'LinearMean']

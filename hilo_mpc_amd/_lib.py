@@ -59,6 +59,20 @@ class LqrOpts(C.Structure):
     _fields_ = [('horizon', C.c_int32), ('max_iter', C.c_int32), ('tol', C.c_double)]
 
 
+class GpFitProblem(C.Structure):
+    """hilo_gp_fit_problem: one training set with one start point; host pointers."""
+    _fields_ = [(n, C.c_int32) for n in ('nf', 'n', 'kprog_len', 'mprog_len', 'n_theta', 'n_map')] + \
+               [(n, C.c_void_p) for n in ('X', 'y', 'kprog', 'mprog', 'map_slot', 'map_theta', 'map_kind', 'map_coef', 'theta0')]
+
+
+class GpFitOpts(C.Structure):
+    """hilo_gp_fit_opts: maxiter 0 = evaluate only."""
+    _fields_ = [('maxiter', C.c_int32), ('reserved', C.c_int32), ('gtol', C.c_double)]
+
+
+GPFIT_MAX_N, GPFIT_MAX_THETA, GPFIT_MAX_PROG, GPFIT_MAX_MAP = 256, 16, 256, 64     # include/hilo_hip.h
+
+
 class NmpcDesc(C.Structure):
     _fields_ = [('model_id', C.c_int32), ('N', C.c_int32), ('Nc', C.c_int32), ('erk_order', C.c_int32),
                 ('n_sub', C.c_int32), ('max_iter', C.c_int32), ('acceptable_iter', C.c_int32), ('reserved', C.c_int32),
@@ -184,6 +198,7 @@ def _declare(lib):
         'hilo_gp_predict': (C.c_int, [vp, i64, vp, i32, vp, vp, vp]),
         'hilo_gp_kernel_matrix': (C.c_int, [i32, i32, vp, i32, i64, vp, i64, vp, vp, vp]),
         'hilo_gp_mean': (C.c_int, [i32, i32, vp, i32, i64, vp, vp, vp]),
+        'hilo_gp_fit_batch': (C.c_int, [i32, i32, P(GpFitProblem), P(GpFitOpts), vp, vp, vp, vp, vp, vp, vp]),
         'hilo_ann_create': (C.c_int, [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, P(vp)]),
         'hilo_ann_destroy': (None, [vp]),
         'hilo_ann_predict': (C.c_int, [vp, i64, vp, i64, vp, i64, vp]),

@@ -289,10 +289,13 @@ __global__ __launch_bounds__(FACT_TPB) void gp_factor_kernel(int n, double* __re
 // share the tiles) - then alpha by blocked forward / backward substitution with the stored inverses of the diagonal blocks, and
 // the log marginal likelihood.  13 block steps instead of 200 column steps (3 barriers each) for n = 200.
 typedef double gpf_v4d __attribute__((ext_vector_type(4)));
-__global__ __launch_bounds__(FACT_TPB) void gp_factor_blocked_kernel(int n, double* __restrict__ A, const double* __restrict__ y,
-                                                                     const double* __restrict__ mu, double* __restrict__ alpha,
-                                                                     double* __restrict__ out /*[2]: lml, info*/) {
-  extern __shared__ double fsm[];
+// The body is shared with gp_fit_batch_kernel below (one objective value of the on-device hyper-parameter fit): `fsm` is the
+// caller's LDS of gp_factor_lds_doubles(n) doubles; A, y, mu, alpha and out may live in global memory or in LDS.  Ends without a
+// barrier after thread 0 wrote `out`.
+__host__ __device__ constexpr size_t gp_factor_lds_doubles(int T) { return 16 * 17 + (size_t)T * 256 + (size_t)T * 16 * 16 + (size_t)T * 16; }
+__device__ __forceinline__ void gp_factor_blocked_body(int n, double* __restrict__ A, const double* __restrict__ y,
+                                                       const double* __restrict__ mu, double* __restrict__ alpha,
+                                                       double* __restrict__ out /*[2]: lml, info*/, double* __restrict__ fsm) {
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6, nwave = FACT_TPB / 64;
   const int T = (n + 15) / 16, np_ = T * 16;
   double* D = fsm;                       // [16][17] diagonal block (then its Cholesky factor)
@@ -452,6 +455,12 @@ __global__ __launch_bounds__(FACT_TPB) void gp_factor_blocked_kernel(int n, doub
     out[0] = tot - 0.5 * n * log(2.0 * M_PI);
     out[1] = (double)bad;
   }
+}
+__global__ __launch_bounds__(FACT_TPB) void gp_factor_blocked_kernel(int n, double* __restrict__ A, const double* __restrict__ y,
+                                                                     const double* __restrict__ mu, double* __restrict__ alpha,
+                                                                     double* __restrict__ out /*[2]: lml, info*/) {
+  extern __shared__ double fsm[];
+  gp_factor_blocked_body(n, A, y, mu, alpha, out, fsm);
 }
 
 // Linv = L^-1, needed by the predictive variance only (built on first use after a fit): one wave per column c, forward
@@ -792,6 +801,282 @@ __global__ __launch_bounds__(256) void gp_predict_reg_kernel(const double* __res
   ss += __shfl_xor(ss, 16, 64);
   ss += __shfl_xor(ss, 32, 64);
   if (g == 0 && qv) var[qi] = eval_kernel(prog_s, klen, Xq + qi, m, Xq + qi, m) - ss + sn2_add;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Hyper-parameter fits of many GPs in one launch (hilo_gp_fit_batch): one workgroup per problem = (training set, start point),
+// the whole quasi-Newton iteration inside the launch.
+//   objective  : kernel program from theta through the slot map (LDS) -> K_y = k(X, X) + sn2 I into the problem's workspace W0
+//                -> gp_factor_blocked_body: L (in place), alpha, LML
+//   gradient   : (accepted points only) L^-1 into W1, the columns dealt over the waves, each wave keeps its column in registers
+//                (lane l owns the entries l, l + 64, ...); K_y^-1 = L^-T L^-1 tile by tile on v_mfma_f64_16x16x4 over the
+//                dead factor in W0 (lower tiles); then per theta_j the trace 1/2 sum (alpha alpha^T - K_y^-1) o dK_y/dtheta_j
+//                with dK_y/dtheta_j by central differences (h = 1e-5) of the covariance function, two perturbed programs in LDS
+//   optimiser  : BFGS on the inverse Hessian with Armijo backtracking, thread 0 on LDS state
+// Every reduction is per-thread strided partials -> wave shuffles -> per-wave LDS slots summed in a fixed order, and there are no
+// atomics: a problem's result depends on nothing but the problem.  Every decision is taken by thread 0, written to LDS and read
+// by all threads after a barrier, so that all waves take every branch together; the loop runs at most 1 + 41 maxiter times.
+constexpr int GPF_NP = HILO_GPFIT_MAX_N, GPF_T = GPF_NP / 16, GPF_NTH = HILO_GPFIT_MAX_THETA, GPF_KMAX = HILO_GPFIT_MAX_PROG,
+              GPF_MAP = HILO_GPFIT_MAX_MAP, GPF_LS = 40;
+constexpr double GPF_H = 1e-5, GPF_C1 = 1e-4;
+struct gpf_problem {   // offsets in doubles into the packed pool / the workspace
+  int nf, n, klen, mlen, n_theta, n_map;
+  long long X, y, kprog, mprog, map /*[n_map][4]: slot, theta index, kind, coef*/, theta0, work;
+};
+struct gpf_state {     // LDS, written by thread 0 only
+  double th[GPF_NTH], tht[GPF_NTH], g[GPF_NTH], gn[GPF_NTH], d[GPF_NTH], H[GPF_NTH * GPF_NTH];
+  double f, ft, step, gd;
+  int iter, nfev, status, fresh, ls, init, ctl, pad;
+};
+constexpr size_t GPF_LDS_DOUBLES = gp_factor_lds_doubles(GPF_T) + 2 * GPF_NP + 4 * GPF_KMAX + 4 * GPF_MAP + 16 + 2 +
+                                   (sizeof(gpf_state) + 7) / 8;
+
+// dst = base program with the mapped slots at theta (+ dh on theta[jp]); ends with a barrier
+__device__ __forceinline__ void gpf_build_prog(double* dst, const double* base, int klen, const double* map, int n_map,
+                                               const double* th, int jp, double dh) {
+  const int t = threadIdx.x;
+  for (int e = t; e < klen; e += FACT_TPB) dst[e] = base[e];
+  __syncthreads();
+  for (int e = t; e < n_map; e += FACT_TPB) {
+    const int j = (int)map[4 * e + 1];
+    const double v = map[4 * e + 3] * (th[j] + (j == jp ? dh : 0.0));
+    dst[(int)map[4 * e]] = (int)map[4 * e + 2] == HILO_GPFIT_EXP ? exp(v) : v;
+  }
+  __syncthreads();
+}
+
+__global__ __launch_bounds__(FACT_TPB) void gp_fit_batch_kernel(const gpf_problem* __restrict__ table, const double* __restrict__ pool,
+                                                                double* __restrict__ work, int maxiter, double gtol,
+                                                                double* __restrict__ theta_out, double* __restrict__ lml_out,
+                                                                double* __restrict__ grad_out, int* __restrict__ info_out /*[P][3]*/) {
+  extern __shared__ double gsm[];
+  const gpf_problem pb = table[blockIdx.x];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, nwave = FACT_TPB / 64;
+  const int n = pb.n, nth = pb.n_theta, klen = pb.klen;
+  const int64_t nn = (int64_t)n * n;
+  double* fsm = gsm;                                       // LDS of the factorisation
+  double* mu_s = fsm + gp_factor_lds_doubles(GPF_T);       // [GPF_NP] m(X)
+  double* alpha_s = mu_s + GPF_NP;                         // [GPF_NP]
+  double* prog_b = alpha_s + GPF_NP;                       // base | working | theta + h e_j | theta - h e_j
+  double* prog_w = prog_b + GPF_KMAX;
+  double* prog_p = prog_w + GPF_KMAX;
+  double* prog_m = prog_p + GPF_KMAX;
+  double* map_s = prog_m + GPF_KMAX;                       // [GPF_MAP][4]
+  double* red = map_s + 4 * GPF_MAP;                       // [16]
+  double* out_s = red + 16;                                // [2]: lml, info of the factorisation
+  gpf_state* S = (gpf_state*)(out_s + 2);
+  const double* X = pool + pb.X;
+  const double* y = pool + pb.y;
+  double* W0 = work + pb.work;                             // K_y -> L -> K_y^-1 (lower tiles)
+  double* W1 = W0 + nn;                                    // L^-1
+  for (int e = t; e < klen; e += FACT_TPB) prog_b[e] = pool[pb.kprog + e];
+  for (int e = t; e < 4 * pb.n_map; e += FACT_TPB) map_s[e] = pool[pb.map + e];
+  for (int i = t; i < n; i += FACT_TPB) mu_s[i] = eval_mean(pool + pb.mprog, pb.mlen, X + i, n);
+  if (t == 0) {
+    for (int j = 0; j < nth; ++j) S->th[j] = S->tht[j] = pool[pb.theta0 + j];
+    S->iter = 0; S->nfev = 0; S->status = HILO_GPFIT_MAXITER; S->fresh = 1; S->ls = 0; S->init = 1; S->ctl = 0;
+    S->f = 0.0; S->step = 0.0; S->gd = 0.0;
+  }
+  __syncthreads();
+  const int T = (n + 15) / 16;
+  const int64_t max_ev = 1 + (int64_t)maxiter * (GPF_LS + 1);
+  for (int64_t ev = 0; ev < max_ev; ++ev) {
+    // ---- objective at S->tht --------------------------------------------------------------------------------------------
+    gpf_build_prog(prog_w, prog_b, klen, map_s, pb.n_map, S->tht, -1, 0.0);
+    {
+      const double sn2 = exp(S->tht[0]);
+      for (int64_t e = t; e < nn; e += FACT_TPB) {
+        const int i = (int)(e / n), j = (int)(e - (int64_t)i * n);
+        double v = eval_kernel(prog_w, klen, X + i, n, X + j, n);
+        if (i == j) v += sn2;
+        W0[e] = v;
+      }
+    }
+    __threadfence_block();
+    __syncthreads();
+    gp_factor_blocked_body(n, W0, y, mu_s, alpha_s, out_s, fsm);
+    __threadfence_block();
+    __syncthreads();
+    if (t == 0) {   // 0 = exit, 1 = rejected trial (S->tht holds the next one), 2 = accepted
+      const double ft = -out_s[0];
+      const bool pd = out_s[1] == 0.0 && isfinite(ft);
+      S->nfev += 1;
+      if (S->init) {
+        if (pd) { S->ft = ft; S->ctl = 2; }
+        else { S->status = HILO_GPFIT_START_NOT_PD; S->ctl = 0; }
+      } else if (pd && ft <= S->f + GPF_C1 * S->step * S->gd) {
+        S->ft = ft; S->ctl = 2;
+      } else if (S->ls >= GPF_LS || S->f + 0.5 * S->step * S->gd == S->f) {
+        // out of halvings, or the first-order change of the objective along the halved step is below the resolution of the
+        // objective's own value: no trial point can show a decrease any more (the noise floor of the central-difference gradient)
+        S->status = HILO_GPFIT_LINESEARCH; S->ctl = 0;
+      } else {
+        S->ls += 1;
+        S->step *= 0.5;
+        for (int j = 0; j < nth; ++j) S->tht[j] = S->th[j] + S->step * S->d[j];
+        S->ctl = 1;
+      }
+    }
+    __syncthreads();
+    const int ctl = S->ctl;
+    if (ctl == 0) break;
+    if (ctl == 1) continue;
+    // ---- gradient at the accepted point S->tht (its factor is in W0, its alpha in alpha_s) ---------------------------------
+    for (int64_t e = t; e < nn; e += FACT_TPB) W1[e] = 0.0;
+    __threadfence_block();
+    __syncthreads();
+    for (int c = wave; c < n; c += nwave) {   // column c of L^-1 by forward substitution, entry j of it in lane j % 64
+      double cr[GPF_NP / 64];
+#pragma unroll
+      for (int k = 0; k < GPF_NP / 64; ++k) cr[k] = 0.0;
+      for (int i = c; i < n; ++i) {
+        const double* Li = W0 + (int64_t)i * n;
+        double s = 0.0;
+#pragma unroll
+        for (int k = 0; k < GPF_NP / 64; ++k) {
+          const int j = lane + 64 * k;
+          if (j >= c && j < i) s += Li[j] * cr[k];
+        }
+        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+        const double v = ((i == c ? 1.0 : 0.0) - s) / Li[i];
+#pragma unroll
+        for (int k = 0; k < GPF_NP / 64; ++k)
+          if (lane + 64 * k == i) cr[k] = v;
+        if (lane == 0) W1[(int64_t)i * n + c] = v;
+      }
+    }
+    __threadfence_block();
+    __syncthreads();
+    {   // K_y^-1[a][b] = sum_k L^-1[k][a] L^-1[k][b], k >= max(a, b): tiles (I >= K) over the factor in W0
+      const int npair = T * (T + 1) / 2, q = lane & 15, g = lane >> 4;
+      for (int pr = wave; pr < npair; pr += nwave) {
+        int I = (int)((sqrt(8.0 * (double)pr + 1.0) - 1.0) * 0.5);
+        while (I * (I + 1) / 2 > pr) --I;
+        while ((I + 1) * (I + 2) / 2 <= pr) ++I;
+        const int K = pr - I * (I + 1) / 2;
+        const int ca = 16 * I + q, cb = 16 * K + q;
+        gpf_v4d acc = {0.0, 0.0, 0.0, 0.0};
+        for (int kb = 4 * I; kb < 4 * T; ++kb) {
+          const int k = 4 * kb + g;
+          const double a = (k < n && ca < n) ? W1[(int64_t)k * n + ca] : 0.0;   // A operand: (L^-1)^T[row q][4 kb + g]
+          const double b = (k < n && cb < n) ? W1[(int64_t)k * n + cb] : 0.0;   // B operand: L^-1[4 kb + g][col q]
+          acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc, 0, 0, 0);
+        }
+#pragma unroll
+        for (int rg = 0; rg < 4; ++rg) {
+          const int gi = 16 * I + 4 * rg + g;
+          if (gi < n && cb < n) W0[(int64_t)gi * n + cb] = acc[rg];
+        }
+      }
+    }
+    __threadfence_block();
+    __syncthreads();
+    for (int j = 0; j < nth; ++j) {
+      gpf_build_prog(prog_p, prog_b, klen, map_s, pb.n_map, S->tht, j, GPF_H);
+      gpf_build_prog(prog_m, prog_b, klen, map_s, pb.n_map, S->tht, j, -GPF_H);
+      const double inv2h = 1.0 / (2.0 * GPF_H);
+      const double dsn2 = j == 0 ? (exp(S->tht[0] + GPF_H) - exp(S->tht[0] - GPF_H)) * inv2h : 0.0;
+      double part = 0.0;
+      for (int64_t e = t; e < nn; e += FACT_TPB) {
+        const int a = (int)(e / n), b = (int)(e - (int64_t)a * n);
+        double dk = (eval_kernel(prog_p, klen, X + a, n, X + b, n) - eval_kernel(prog_m, klen, X + a, n, X + b, n)) * inv2h;
+        if (a == b) dk += dsn2;
+        const int hi = a > b ? a : b, lo = a > b ? b : a;
+        part += (alpha_s[a] * alpha_s[b] - W0[(int64_t)hi * n + lo]) * dk;
+      }
+      for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o, 64);
+      if (lane == 0) red[wave] = part;
+      __syncthreads();
+      if (t == 0) {
+        double tot = 0.0;
+        for (int w = 0; w < nwave; ++w) tot += red[w];
+        S->gn[j] = -0.5 * tot;   // gradient of the minimised -LML
+      }
+      __syncthreads();
+    }
+    if (t == 0) {   // BFGS update, stop rules, next direction and first trial point
+      if (S->init) {
+        S->init = 0;
+        for (int i = 0; i < nth * nth; ++i) S->H[i] = 0.0;
+        for (int i = 0; i < nth; ++i) S->H[i * nth + i] = 1.0;
+      } else {
+        double s[GPF_NTH], yv[GPF_NTH], Hy[GPF_NTH];
+        double sy = 0.0, ss = 0.0, yy = 0.0;
+        for (int i = 0; i < nth; ++i) {
+          s[i] = S->tht[i] - S->th[i];
+          yv[i] = S->gn[i] - S->g[i];
+          sy += s[i] * yv[i]; ss += s[i] * s[i]; yy += yv[i] * yv[i];
+        }
+        if (sy > 1e-12 * sqrt(ss) * sqrt(yy)) {
+          if (S->fresh) {
+            const double sc = sy / yy;
+            for (int i = 0; i < nth; ++i) S->H[i * nth + i] = sc;
+            S->fresh = 0;
+          }
+          // H <- (I - rho s y^T) H (I - rho y s^T) + rho s s^T = H - rho (s Hy^T + Hy s^T) + (rho^2 y^T H y + rho) s s^T
+          const double rho = 1.0 / sy;
+          double yHy = 0.0;
+          for (int i = 0; i < nth; ++i) {
+            double v = 0.0;
+            for (int k = 0; k < nth; ++k) v += S->H[i * nth + k] * yv[k];
+            Hy[i] = v;
+          }
+          for (int i = 0; i < nth; ++i) yHy += yv[i] * Hy[i];
+          const double cc = rho * rho * yHy + rho;
+          for (int i = 0; i < nth; ++i)
+            for (int k = 0; k < nth; ++k) S->H[i * nth + k] += -rho * (s[i] * Hy[k] + Hy[i] * s[k]) + cc * s[i] * s[k];
+        }
+        S->iter += 1;
+      }
+      double gmax = 0.0, g2 = 0.0;
+      for (int i = 0; i < nth; ++i) {
+        S->th[i] = S->tht[i];
+        S->g[i] = S->gn[i];
+        gmax = fmax(gmax, fabs(S->g[i]));
+        g2 += S->g[i] * S->g[i];
+      }
+      S->f = S->ft;
+      if (!(gmax > gtol)) { S->status = HILO_GPFIT_CONVERGED; S->ctl = 0; }
+      else if (S->iter >= maxiter) { S->status = HILO_GPFIT_MAXITER; S->ctl = 0; }
+      else {
+        double gd = 0.0;
+        for (int i = 0; i < nth; ++i) {
+          double v = 0.0;
+          for (int k = 0; k < nth; ++k) v += S->H[i * nth + k] * S->g[k];
+          S->d[i] = -v;
+          gd += S->g[i] * S->d[i];
+        }
+        if (!(gd < 0.0)) {   // not a descent direction: back to steepest descent
+          for (int i = 0; i < nth * nth; ++i) S->H[i] = 0.0;
+          for (int i = 0; i < nth; ++i) { S->H[i * nth + i] = 1.0; S->d[i] = -S->g[i]; }
+          gd = -g2;
+          S->fresh = 1;
+        }
+        S->gd = gd;
+        S->step = S->iter == 0 ? fmin(1.0, 1.0 / sqrt(g2)) : 1.0;
+        S->ls = 0;
+        for (int i = 0; i < nth; ++i) S->tht[i] = S->th[i] + S->step * S->d[i];
+        S->ctl = 1;
+        if (S->f + S->step * gd == S->f) { S->status = HILO_GPFIT_LINESEARCH; S->ctl = 0; }   // see the line search above
+      }
+    }
+    __syncthreads();
+    if (S->ctl == 0) break;
+  }
+  __syncthreads();
+  if (t == 0) {
+    int* info = info_out + 3 * (int64_t)blockIdx.x;
+    info[2] = S->status;
+    if (S->status != HILO_GPFIT_START_NOT_PD) {
+      info[0] = S->iter;
+      info[1] = S->nfev;
+      lml_out[blockIdx.x] = -S->f;
+      for (int j = 0; j < nth; ++j) {
+        theta_out[(int64_t)blockIdx.x * GPF_NTH + j] = S->th[j];
+        grad_out[(int64_t)blockIdx.x * GPF_NTH + j] = -S->g[j];
+      }
+    }
+  }
 }
 
 // host-side validation of a program: returns 0 when well formed, sets max stack depth
@@ -1200,5 +1485,138 @@ extern "C" int hilo_gp_mean(int device, int nf, const double* mprog_host, int ml
   if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
   (void)hipFree(dprog);
   if (e != hipSuccess) return fail(HILO_EHIP, "mean launch failed: %s", hipGetErrorString(e));
+  return HILO_OK;
+}
+
+// Fits of many GPs in one launch: packs the problems (training sets, programs, slot maps, start points) into one device pool,
+// launches one workgroup per problem and reads the results back (include/hilo_hip.h).
+extern "C" int hilo_gp_fit_batch(int device, int n_problems, const hilo_gp_fit_problem* problems, const hilo_gp_fit_opts* options,
+                                 double* theta_out, double* lml_out, double* grad_out, int32_t* iters_out, int32_t* nfev_out,
+                                 int32_t* status_out, void* stream) {
+  HILO_REQUIRE(problems && options && theta_out && lml_out && grad_out && iters_out && nfev_out && status_out,
+               "hilo_gp_fit_batch: NULL argument");
+  HILO_REQUIRE(n_problems >= 0, "hilo_gp_fit_batch: negative problem count");
+  HILO_REQUIRE(options->maxiter >= 0 && options->maxiter <= 100000, "hilo_gp_fit_batch: maxiter %d out of range (0..100000)", options->maxiter);
+  HILO_REQUIRE(options->gtol >= 0.0, "hilo_gp_fit_batch: gtol must not be negative");
+  if (n_problems == 0) return HILO_OK;
+  const int P = n_problems;
+  gpf_problem* tab = new gpf_problem[P];
+  size_t pool_len = 0, work_len = 0;
+  int rc = HILO_OK;
+  for (int p = 0; p < P && rc == HILO_OK; ++p) {
+    const hilo_gp_fit_problem& q = problems[p];
+    if (!(q.X && q.y && q.kprog && q.mprog && q.theta0) || (q.n_map > 0 && !(q.map_slot && q.map_theta && q.map_kind && q.map_coef)))
+      rc = fail(HILO_EINVAL, "hilo_gp_fit_batch: problem %d has a NULL pointer", p);
+    else if (q.nf < 1 || q.n < 1 || q.n_theta < 1 || q.n_map < 0 || q.kprog_len < 1 || q.mprog_len < 1)
+      rc = fail(HILO_EINVAL, "hilo_gp_fit_batch: problem %d needs nf, n, n_theta, program lengths >= 1 and n_map >= 0", p);
+    else if (q.n > HILO_GPFIT_MAX_N)
+      rc = fail(HILO_ENOTSUP, "hilo_gp_fit_batch: problem %d has n = %d training points, the batched fit is built for n <= %d", p, q.n,
+                HILO_GPFIT_MAX_N);
+    else if (q.n_theta > HILO_GPFIT_MAX_THETA)
+      rc = fail(HILO_ENOTSUP, "hilo_gp_fit_batch: problem %d has %d free hyper-parameters, the batched fit is built for <= %d", p,
+                q.n_theta, HILO_GPFIT_MAX_THETA);
+    else if (q.kprog_len > HILO_GPFIT_MAX_PROG || q.n_map > HILO_GPFIT_MAX_MAP)
+      rc = fail(HILO_ENOTSUP, "hilo_gp_fit_batch: problem %d has a kernel program of %d entries with %d mapped slots, the LDS copy "
+                              "holds %d and %d", p, q.kprog_len, q.n_map, HILO_GPFIT_MAX_PROG, HILO_GPFIT_MAX_MAP);
+    if (rc == HILO_OK) rc = check_prog(q.kprog, q.kprog_len, false, q.nf);
+    if (rc == HILO_OK) rc = check_prog(q.mprog, q.mprog_len, true, q.nf);
+    if (rc != HILO_OK) break;
+    // a mapped slot must be a parameter entry of a node: the structure of the program is not the optimiser's to change
+    bool is_par[HILO_GPFIT_MAX_PROG];
+    for (int e = 0; e < q.kprog_len; ++e) is_par[e] = false;
+    for (int pos = 0; pos < q.kprog_len;) {
+      const int na = (int)q.kprog[pos + 1], npar = (int)q.kprog[pos + 2 + na];
+      for (int e = 0; e < npar; ++e) is_par[pos + 3 + na + e] = true;
+      pos += 3 + na + npar;
+    }
+    for (int e = 0; e < q.n_map && rc == HILO_OK; ++e) {
+      if (q.map_slot[e] < 0 || q.map_slot[e] >= q.kprog_len || !is_par[q.map_slot[e]])
+        rc = fail(HILO_EINVAL, "hilo_gp_fit_batch: problem %d, map entry %d: slot %d is not a parameter of the kernel program", p, e, q.map_slot[e]);
+      else if (q.map_theta[e] < 0 || q.map_theta[e] >= q.n_theta)
+        rc = fail(HILO_EINVAL, "hilo_gp_fit_batch: problem %d, map entry %d: theta index %d out of range", p, e, q.map_theta[e]);
+      else if (q.map_kind[e] != HILO_GPFIT_EXP && q.map_kind[e] != HILO_GPFIT_LIN)
+        rc = fail(HILO_EINVAL, "hilo_gp_fit_batch: problem %d, map entry %d: unknown kind %d", p, e, q.map_kind[e]);
+    }
+    gpf_problem& d = tab[p];
+    d.nf = q.nf; d.n = q.n; d.klen = q.kprog_len; d.mlen = q.mprog_len; d.n_theta = q.n_theta; d.n_map = q.n_map;
+    d.X = (long long)pool_len; pool_len += (size_t)q.nf * q.n;
+    d.y = (long long)pool_len; pool_len += q.n;
+    d.kprog = (long long)pool_len; pool_len += q.kprog_len;
+    d.mprog = (long long)pool_len; pool_len += q.mprog_len;
+    d.map = (long long)pool_len; pool_len += 4 * (size_t)q.n_map;
+    d.theta0 = (long long)pool_len; pool_len += q.n_theta;
+    d.work = (long long)work_len; work_len += 2 * (size_t)q.n * q.n;
+  }
+  if (rc != HILO_OK) { delete[] tab; return rc; }
+  double* pool = new double[pool_len];
+  for (int p = 0; p < P; ++p) {
+    const hilo_gp_fit_problem& q = problems[p];
+    const gpf_problem& d = tab[p];
+    memcpy(pool + d.X, q.X, sizeof(double) * (size_t)q.nf * q.n);
+    memcpy(pool + d.y, q.y, sizeof(double) * q.n);
+    memcpy(pool + d.kprog, q.kprog, sizeof(double) * q.kprog_len);
+    memcpy(pool + d.mprog, q.mprog, sizeof(double) * q.mprog_len);
+    for (int e = 0; e < q.n_map; ++e) {
+      pool[d.map + 4 * e] = q.map_slot[e]; pool[d.map + 4 * e + 1] = q.map_theta[e];
+      pool[d.map + 4 * e + 2] = q.map_kind[e]; pool[d.map + 4 * e + 3] = q.map_coef[e];
+    }
+    memcpy(pool + d.theta0, q.theta0, sizeof(double) * q.n_theta);
+  }
+  hipStream_t s = (hipStream_t)stream;
+  gpf_problem* d_tab = nullptr;
+  double *d_pool = nullptr, *d_work = nullptr, *d_out = nullptr;
+  int* d_info = nullptr;
+  const size_t out_len = (size_t)P * (2 * GPF_NTH + 1);
+  double* h_out = new double[out_len];
+  int* h_info = new int[3 * (size_t)P];
+  hipError_t e = hipSetDevice(device);
+  size_t free_b = 0, total_b = 0;
+  if (e == hipSuccess) e = hipMemGetInfo(&free_b, &total_b);
+  const size_t work_bytes = work_len * sizeof(double);
+  if (e == hipSuccess && work_bytes + (pool_len + out_len) * sizeof(double) > free_b) {
+    delete[] tab; delete[] pool; delete[] h_out; delete[] h_info;
+    return fail(HILO_ENOMEM, "hilo_gp_fit_batch: the workspace of %d problems (2 n^2 doubles each) is %zu bytes, the device has %zu free",
+                P, work_bytes, free_b);
+  }
+  if (e == hipSuccess) e = hipMalloc((void**)&d_tab, sizeof(gpf_problem) * P);
+  if (e == hipSuccess) e = hipMalloc((void**)&d_pool, sizeof(double) * pool_len);
+  if (e == hipSuccess) e = hipMalloc((void**)&d_work, work_bytes);
+  if (e == hipSuccess) e = hipMalloc((void**)&d_out, sizeof(double) * out_len);
+  if (e == hipSuccess) e = hipMalloc((void**)&d_info, sizeof(int) * 3 * P);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_tab, tab, sizeof(gpf_problem) * P, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_pool, pool, sizeof(double) * pool_len, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemsetAsync(d_out, 0, sizeof(double) * out_len, s);
+  if (e == hipSuccess) e = hipMemsetAsync(d_info, 0, sizeof(int) * 3 * P, s);
+  if (e == hipSuccess) {
+    const size_t lds = GPF_LDS_DOUBLES * sizeof(double);
+    e = hipFuncSetAttribute((const void*)gp_fit_batch_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e == hipSuccess) {
+      double* d_theta = d_out;
+      double* d_grad = d_out + (size_t)P * GPF_NTH;
+      double* d_lml = d_grad + (size_t)P * GPF_NTH;
+      hipLaunchKernelGGL(gp_fit_batch_kernel, dim3(P), dim3(FACT_TPB), lds, s, d_tab, d_pool, d_work, (int)options->maxiter,
+                         options->gtol, d_theta, d_lml, d_grad, d_info);
+      e = hipGetLastError();
+    }
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(h_out, d_out, sizeof(double) * out_len, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(h_info, d_info, sizeof(int) * 3 * P, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  (void)hipFree(d_tab); (void)hipFree(d_pool); (void)hipFree(d_work); (void)hipFree(d_out); (void)hipFree(d_info);
+  if (e == hipSuccess) {
+    for (int p = 0; p < P; ++p) {
+      status_out[p] = h_info[3 * p + 2];
+      if (status_out[p] == HILO_GPFIT_START_NOT_PD) continue;   // nothing but the status
+      iters_out[p] = h_info[3 * p];
+      nfev_out[p] = h_info[3 * p + 1];
+      lml_out[p] = h_out[(size_t)P * 2 * GPF_NTH + p];
+      for (int j = 0; j < tab[p].n_theta; ++j) {
+        theta_out[(size_t)p * GPF_NTH + j] = h_out[(size_t)p * GPF_NTH + j];
+        grad_out[(size_t)p * GPF_NTH + j] = h_out[(size_t)P * GPF_NTH + (size_t)p * GPF_NTH + j];
+      }
+    }
+  }
+  delete[] tab; delete[] pool; delete[] h_out; delete[] h_info;
+  if (e != hipSuccess) return fail(HILO_EHIP, "hilo_gp_fit_batch: %s", hipGetErrorString(e));
   return HILO_OK;
 }

@@ -9,7 +9,8 @@ Inputs are feature-major (n_features x n_observations) exactly like the referenc
 A kernel/mean tree is compiled to a flat postfix program (opcodes in include/hilo_hip.h) that the device
 interprets; the numeric work (covariance matrices, Cholesky, alpha, L^-1, predictions) is done by
 libhilo_hip.so only.  Hyper-parameter fitting (`fit_model`) drives the device log marginal likelihood
-from a host quasi-Newton loop; an analytic device gradient is the next step.
+from a host quasi-Newton loop.  `GPArray` holds one GP per label and fits all of them, from several start points each, in one
+launch (`hilo_gp_fit_batch`: the whole quasi-Newton iteration on the device, one workgroup per problem).
 """
 import ctypes as C
 from math import factorial, gamma as gamma_fun
@@ -24,6 +25,8 @@ from ._device import device, to_dev, ptr, stream_ptr
 K_CONST, K_GAMMAEXP, K_MATERN, K_RQ, K_PP, K_POLY, K_NN, K_PERIODIC = range(8)
 K_SUM, K_PRODUCT, K_POWER, K_XX_BEGIN = 16, 17, 18, 19
 M_CONST, M_POLY, M_SUM, M_PRODUCT, M_POWER, M_SCALE = 32, 33, 48, 49, 50, 51
+# kinds of a slot-map entry (HILO_GPFIT_EXP / HILO_GPFIT_LIN): program[slot] = exp(coef * theta) or coef * theta
+MAP_EXP, MAP_LIN = 0, 1
 
 
 def _is_list_like(v):
@@ -200,6 +203,15 @@ class Kernel:
     def program(self, nf):
         raise NotImplementedError
 
+    def program_map(self, nf):
+        """Slot map of `program(nf)`, parallel to `hyperparameter_handles()`: per scalar hyper-parameter the list of
+        `(slot, kind, coef)` with program[slot] = exp(coef * theta) (`MAP_EXP`) or coef * theta (`MAP_LIN`), theta = log(value).
+        It is what lets the device rebuild the program from the optimisation variables of `GPArray.fit_model`."""
+        raise NotImplementedError
+
+    def _par0(self, nf):
+        return 3 + len(self._active(nf))                # [opcode, n_active, active dims..., n_par | parameters...]
+
     def __call__(self, X, X_bar=None):
         """Covariance matrix K[i, j] = k(X[:, i], X_bar[:, j]) (kernel.py:97-140)."""
         host = not isinstance(X, torch.Tensor)
@@ -276,6 +288,9 @@ class ConstantKernel(Kernel):
     def program(self, nf):
         return _node(K_CONST, [], [np.exp(2 * _log(self.bias))])
 
+    def program_map(self, nf):
+        return [[(3, MAP_EXP, 2.)]]
+
 
 class StationaryKernel(Kernel):
     """kernel.py:488-562."""
@@ -305,6 +320,20 @@ class StationaryKernel(Kernel):
         if ll.size != n_active:
             raise ValueError("Length scales vector dimension does not equal input space dimension.")
         return list(np.exp(-2 * ll))
+
+    def _map_M(self, nf, offset):
+        """Entries of the length scales, M = exp(-2 log l) from parameter `offset` of the node on: one hyper-parameter for all
+        slots (isotropic) or one per slot (ARD)."""
+        first = self._par0(nf) + offset
+        slots = [(first + k, MAP_EXP, -2.) for k in range(len(self._active(nf)))]
+        return [slots] if self.is_isotropic() else [[e] for e in slots]
+
+    _M_offset = 3                                       # position of M among the node's parameters
+    _extra_map = ()                                     # further hyper-parameters after the signal variance: parameter positions
+
+    def program_map(self, nf):
+        p0 = self._par0(nf)
+        return self._map_M(nf, self._M_offset) + [[(p0, MAP_EXP, 1.)]] + [[(p0 + k, MAP_EXP, 1.)] for k in self._extra_map]
 
 
 class GammaExponentialKernel(StationaryKernel):
@@ -378,6 +407,8 @@ class MaternKernel(StationaryKernel):
         sf2 = np.exp(2 * _log(self.signal_variance, True))
         return _node(K_MATERN, ad, [sf2, np.sqrt(2 * (self._p + .5)), len(poly)] + poly + self._M(len(ad)))
 
+    _M_offset = property(lambda self: 3 + len(self._poly()))
+
 
 class ExponentialKernel(MaternKernel):
     acronym = "E"
@@ -414,6 +445,9 @@ class RationalQuadraticKernel(StationaryKernel):
         ad = self._active(nf)
         sf2 = np.exp(2 * _log(self.signal_variance, True))
         return _node(K_RQ, ad, [sf2, np.exp(_log(self.alpha))] + self._M(len(ad)))
+
+    _M_offset = 2
+    _extra_map = (1,)
 
 
 class PiecewisePolynomialKernel(StationaryKernel):
@@ -464,6 +498,10 @@ class PolynomialKernel(DotProductKernel):
         sf2 = np.exp(2 * _log(self.signal_variance, True))
         return _node(K_POLY, self._active(nf), [sf2, np.exp(_log(self.offset)), self.degree])
 
+    def program_map(self, nf):
+        p0 = self._par0(nf)
+        return [[(p0 + k, MAP_EXP, 1.)] for k in range(len(self._hyper))]      # signal variance (, offset)
+
 
 class LinearKernel(PolynomialKernel):
     """kernel.py:1237-1259 (degree 1, offset 0)."""
@@ -489,6 +527,10 @@ class NeuralNetworkKernel(Kernel):
         return _node(K_NN, self._active(nf), [np.exp(2 * _log(self.signal_variance, True)),
                                              np.exp(2 * _log(self.weight_variance, True))])
 
+    def program_map(self, nf):
+        p0 = self._par0(nf)
+        return [[(p0, MAP_EXP, 1.)], [(p0 + 1, MAP_EXP, 1.)]]
+
 
 class PeriodicKernel(Kernel):
     """kernel.py:1335-1423 (scalar expression only for one active dimension)."""
@@ -507,6 +549,10 @@ class PeriodicKernel(Kernel):
             raise ValueError("The periodic covariance function is only defined for one active dimension")
         return _node(K_PERIODIC, ad, [2 * _log(self.signal_variance, True), np.exp(_log(self.length_scales)),
                                       np.exp(_log(self.period))])
+
+    def program_map(self, nf):
+        p0 = self._par0(nf)
+        return [[(p0, MAP_LIN, 1.)], [(p0 + 1, MAP_EXP, 1.)], [(p0 + 2, MAP_EXP, 1.)]]
 
 
 class KernelOperator(Kernel):
@@ -530,6 +576,16 @@ class KernelOperator(Kernel):
         out = self.kernel_1.hyperparameter_names if isinstance(self.kernel_1, Kernel) else []
         return out + (self.kernel_2.hyperparameter_names if isinstance(self.kernel_2, Kernel) else [])
 
+    _lead = 0                                           # program entries in front of the first child's
+
+    def program_map(self, nf):
+        out, pos = [], self._lead
+        for k in (self.kernel_1, self.kernel_2):
+            if isinstance(k, Kernel):
+                out += [[(slot + pos, kind, c) for slot, kind, c in entry] for entry in k.program_map(nf)]
+                pos += len(k.program(nf))
+        return out
+
 
 class Sum(KernelOperator):
     def program(self, nf):
@@ -543,6 +599,8 @@ class Product(KernelOperator):
 
 class Power(KernelOperator):
     """kernel.py:1630-1666 - evaluates its child at (x, x) (`self.kernel_1(x)`, :1651)."""
+
+    _lead = 3                                           # the K_XX_BEGIN node; `power` is not a hyper-parameter
 
     def __init__(self, kernel, power):
         super().__init__(kernel)
@@ -1075,3 +1133,266 @@ class GaussianProcess:
         if host:
             return mean.cpu().numpy(), (var.cpu().numpy() if return_var else None)
         return mean, var
+
+
+# =================================================================================================
+# GPArray (gp.py:974-1015) + one-launch hyper-parameter fit of all members
+# =================================================================================================
+FIT_STATUS = {0: 'converged', 1: 'maximum number of iterations reached', 2: 'line search found no decrease (noise floor of the objective reached)',
+              3: 'start point not positive definite'}
+
+
+class GPArray:
+    """Container of `n_gps` Gaussian processes, one per label (gp.py:974-1015: `__len__`, `__iter__`, `__getitem__`), whose
+    hyper-parameters are fitted together: `fit_model` maximises the log marginal likelihood of every member from every start
+    point in ONE launch of `hilo_gp_fit_batch` - one workgroup per (member, start), the whole BFGS iteration on the device.
+    Members are ordinary `GaussianProcess` objects with their own handles; `setup`, `log_marginal_likelihood` and `predict` loop
+    over them (a batched predict kernel does not exist: a prediction is one launch per member)."""
+    __array_ufunc__ = None
+
+    def __init__(self, n_gps):
+        self._n_gps = int(n_gps)
+        self._gps = np.empty((self._n_gps, 1), dtype=object)
+        self.fit_stats = None
+
+    def __len__(self):
+        return self._n_gps
+
+    def __iter__(self):
+        for k in range(self._n_gps):
+            gp = self._gps[k, 0]
+            if gp is None:
+                gp = object.__new__(GaussianProcess)
+                self._gps[k, 0] = gp
+            yield gp
+
+    def __getitem__(self, item):
+        return self._gps[item, 0]
+
+    def __setitem__(self, item, gp):
+        if not isinstance(gp, GaussianProcess):
+            raise TypeError("The members of a GPArray are GaussianProcess objects")
+        self._gps[item, 0] = gp
+
+    @classmethod
+    def from_labels(cls, features, labels, kernel=None, mean=None, noise_variance=1.):
+        """One `GaussianProcess` per label over the same features.  `kernel` / `mean`: one object that is copied for every member,
+        or a list with one per label; `noise_variance`: a number or one per label."""
+        import copy
+        labels = list(labels) if _is_list_like(labels) else [labels]
+        n = len(labels)
+
+        def per_label(v, what):
+            if isinstance(v, (list, tuple)):
+                if len(v) != n:
+                    raise ValueError(f"Dimension mismatch. Got {len(v)} {what} for {n} labels.")
+                return list(v)
+            return [copy.deepcopy(v) for _ in range(n)]
+        kernels, means = per_label(kernel, 'kernels'), per_label(mean, 'means')
+        noise = per_label(noise_variance.tolist() if isinstance(noise_variance, np.ndarray) else noise_variance, 'noise variances')
+        arr = cls(n)
+        for k in range(n):
+            arr[k] = GaussianProcess(features, [labels[k]], kernel=kernels[k], mean=means[k], noise_variance=noise[k])
+        return arr
+
+    def _members(self):
+        out = [self._gps[k, 0] for k in range(self._n_gps)]
+        if any(g is None or not hasattr(g, 'kernel') for g in out):
+            raise RuntimeError("The GPArray has empty members. Fill every slot with a GaussianProcess first.")
+        return out
+
+    def set_training_data(self, X, Y):
+        """X (n_features x n) for every member, Y (n_labels x n): row g is the training target of member g - the pair
+        `DataSet.train_data` returns."""
+        Y = np.atleast_2d(np.asarray(Y.cpu() if isinstance(Y, torch.Tensor) else Y, dtype=float))
+        if Y.shape[0] != self._n_gps:
+            raise ValueError(f"Dimension mismatch. Supplied dimension for the labels is {Y.shape[0]}, but required dimension is "
+                             f"{self._n_gps}.")
+        for g, gp in enumerate(self._members()):
+            gp.set_training_data(X, Y[g:g + 1])
+
+    def setup(self, device_index=None, **kwargs):
+        for gp in self._members():
+            gp.setup(device_index=device_index, **kwargs)
+
+    def log_marginal_likelihood(self):
+        return np.array([gp.log_marginal_likelihood() for gp in self._members()])
+
+    def predict(self, X_query, noise_free=False):
+        """(mean [G, m], var [G, m]): row g is member g's prediction at the m query points.  One launch per member through its
+        own handle - a batched predict kernel is out of scope here."""
+        res = [gp.predict(X_query, noise_free=noise_free) for gp in self._members()]
+        if isinstance(res[0][0], torch.Tensor):
+            return torch.cat([m for m, _ in res], 0), torch.cat([v for _, v in res], 0)
+        return np.concatenate([m for m, _ in res], 0), np.concatenate([v for _, v in res], 0)
+
+    # ---- the batched fit -------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _fit_problem(g, gp):
+        """Everything the device needs of member g: checks what it cannot do and names the way round."""
+        route = f"use GaussianProcess.fit_model of member {g}"
+        if not gp.is_setup():
+            raise NotImplementedError(f"member {g} of the GPArray is not set up: run setup() first, or {route}")
+        if getattr(gp, '_priors', None):
+            raise NotImplementedError(f"member {g} has hyper-priors, which the batched fit does not evaluate: {route}")
+        if gp.mean.hyperparameter_handles():
+            raise NotImplementedError(f"member {g} has free hyper-parameters of the mean function, which the batched fit does not "
+                                      f"optimise (fix them with bounds='fixed'): {route}")
+        bnd = [None] + list(gp.kernel.hyperparameter_bounds())
+        if any(b is not None and b != 'fixed' for b in bnd):
+            raise NotImplementedError(f"member {g} has boxed bounds, which the batched fit does not handle ('fixed' is supported): "
+                                      f"{route}")
+        nf, n = gp._X_train.shape
+        free = [i for i, b in enumerate(bnd) if b != 'fixed']
+        th_all = np.log(np.asarray(gp.hyperparameter_values, dtype=float))
+        if not np.all(np.isfinite(th_all[free])):
+            raise ValueError(f"member {g}: hyper-parameters must be positive to be fitted in log space")
+        kprog = np.ascontiguousarray(gp.kernel.program(nf), dtype=np.float64)
+        mprog = np.ascontiguousarray(gp.mean.program(nf), dtype=np.float64)
+        entries = []
+        for i, entry in enumerate(gp.kernel.program_map(nf)):
+            if i + 1 in free:
+                entries += [(slot, free.index(i + 1), kind, c) for slot, kind, c in entry]
+        if n > _lib.GPFIT_MAX_N:
+            raise NotImplementedError(f"member {g} has {n} training points, the batched fit is built for n <= {_lib.GPFIT_MAX_N}: {route}")
+        if len(free) > _lib.GPFIT_MAX_THETA or kprog.size > _lib.GPFIT_MAX_PROG or len(entries) > _lib.GPFIT_MAX_MAP:
+            raise NotImplementedError(f"member {g} has {len(free)} free hyper-parameters and a kernel program of {kprog.size} entries "
+                                      f"({len(entries)} mapped); the batched fit is built for <= {_lib.GPFIT_MAX_THETA}, "
+                                      f"{_lib.GPFIT_MAX_PROG} and {_lib.GPFIT_MAX_MAP}: {route}")
+        return {'nf': nf, 'n': n, 'free': free, 'theta_all': th_all, 'kprog': kprog, 'mprog': mprog,
+                'X': np.ascontiguousarray(gp._X_train, dtype=np.float64), 'y': np.ascontiguousarray(gp._y_train.ravel(), dtype=np.float64),
+                'slot': np.array([e[0] for e in entries], dtype=np.int32), 'theta': np.array([e[1] for e in entries], dtype=np.int32),
+                'kind': np.array([e[2] for e in entries], dtype=np.int32), 'coef': np.array([e[3] for e in entries], dtype=np.float64)}
+
+    def _start_points(self, problems, n_restarts=1, starts=None, seed=0, spread=1.):
+        """Per member the start points [R, n_free] as LOGS.  Without `starts`: row 0 = the member's current hyper-parameters, rows
+        1.. = row 0 + spread * N(0, 1) from `numpy.random.default_rng([seed, member])` - a function of the seed alone."""
+        if n_restarts < 1:
+            raise ValueError("n_restarts must be at least 1")
+        given = {}
+        if isinstance(starts, dict):
+            given = dict(starts)
+        elif starts is not None:
+            arr = list(starts) if isinstance(starts, (list, tuple)) else starts
+            if np.ndim(arr[0]) == 2 if len(arr) else False:
+                if len(arr) != self._n_gps:
+                    raise ValueError(f"Dimension mismatch. Got start points for {len(arr)} members, the array has {self._n_gps}.")
+                given = dict(enumerate(arr))
+            else:
+                given = {g: arr for g in range(self._n_gps)}
+        if any(not (isinstance(g, (int, np.integer)) and 0 <= g < self._n_gps) for g in given):
+            raise KeyError(f"start points are given per member index 0..{self._n_gps - 1}")
+        out = []
+        for g, pb in enumerate(problems):
+            nth = len(pb['free'])
+            if g in given:
+                v = np.atleast_2d(np.asarray(given[g], dtype=float))
+                if v.ndim != 2 or v.shape[1] != nth or v.shape[0] < 1:
+                    raise ValueError(f"Dimension mismatch. Start points of member {g} need shape [R, {nth}] (noise variance first, then "
+                                     f"the free kernel hyper-parameters), got {v.shape}.")
+                if not np.all(v > 0.):
+                    raise ValueError("start points are hyper-parameter VALUES and must be positive")
+                out.append(np.log(v))
+            else:
+                th0 = pb['theta_all'][pb['free']]
+                rng = np.random.default_rng([int(seed), g])
+                out.append(np.vstack([th0[None, :], th0[None, :] + float(spread) * rng.standard_normal((n_restarts - 1, nth))]))
+        return out
+
+    def _launch(self, problems, thetas, gtol, maxiter):
+        """One launch for all (member, start) pairs; returns per member the arrays theta [R, nth], lml, grad, iters, nfev, status."""
+        P = sum(t.shape[0] for t in thetas)
+        descs = (_lib.GpFitProblem * P)()
+        keep, p = [], 0
+        for pb, th in zip(problems, thetas):
+            th = np.ascontiguousarray(th, dtype=np.float64)
+            keep.append(th)
+            for r in range(th.shape[0]):
+                d = descs[p]
+                d.nf, d.n, d.kprog_len, d.mprog_len, d.n_theta, d.n_map = pb['nf'], pb['n'], pb['kprog'].size, pb['mprog'].size, th.shape[1], \
+                    pb['slot'].size
+                d.X, d.y, d.kprog, d.mprog = pb['X'].ctypes.data, pb['y'].ctypes.data, pb['kprog'].ctypes.data, pb['mprog'].ctypes.data
+                d.map_slot, d.map_theta, d.map_kind, d.map_coef = pb['slot'].ctypes.data, pb['theta'].ctypes.data, pb['kind'].ctypes.data, \
+                    pb['coef'].ctypes.data
+                d.theta0 = th.ctypes.data + r * th.shape[1] * 8
+                p += 1
+        opts = _lib.GpFitOpts(int(maxiter), 0, float(gtol))
+        W = _lib.GPFIT_MAX_THETA
+        theta = np.full((P, W), np.nan)
+        grad = np.full((P, W), np.nan)
+        lml = np.full(P, np.nan)
+        iters, nfev, status = np.full(P, -1, dtype=np.int32), np.full(P, -1, dtype=np.int32), np.full(P, -1, dtype=np.int32)
+        dev = self._members()[0]._dev
+        rc = _lib.lib().hilo_gp_fit_batch(dev.index, P, descs, C.byref(opts), theta.ctypes.data, lml.ctypes.data, grad.ctypes.data,
+                                          iters.ctypes.data, nfev.ctypes.data, status.ctypes.data, None)
+        if rc == -4:
+            raise NotImplementedError(_lib.lib().hilo_last_error().decode(errors='replace'))
+        if rc == -3:
+            raise MemoryError(_lib.lib().hilo_last_error().decode(errors='replace'))
+        _lib.check(rc)
+        out, p = [], 0
+        for th in keep:
+            R, nth = th.shape
+            out.append({'theta': theta[p:p + R, :nth].copy(), 'lml': lml[p:p + R].copy(), 'grad': grad[p:p + R, :nth].copy(),
+                        'iterations': iters[p:p + R].copy(), 'evaluations': nfev[p:p + R].copy(), 'status': status[p:p + R].copy()})
+            p += R
+        return out
+
+    def lml_and_gradient(self):
+        """Log marginal likelihood [G] and its gradient with respect to the logarithms of the free hyper-parameters (noise
+        variance first) of every member at its current hyper-parameters - the batched kernel with `maxiter=0`."""
+        problems = [self._fit_problem(g, gp) for g, gp in enumerate(self._members())]
+        res = self._launch(problems, [pb['theta_all'][pb['free']][None, :] for pb in problems], 0., 0)
+        return np.array([r['lml'][0] for r in res]), [r['grad'][0] for r in res]
+
+    def fit_model(self, n_restarts=1, starts=None, seed=0, spread=1., gtol=1e-6, maxiter=200):
+        """Fits the hyper-parameters of every member from `n_restarts` start points each, all G x R problems in one launch.
+        Restart 0 of a member is its current hyper-parameters, the others add `spread * N(0, 1)` to their logarithms
+        (`numpy.random.default_rng`, a function of `seed`); `starts` ([R, n_free] values for all members, a list with one such
+        array per member, or a dict member -> array) gives them explicitly, noise variance first.  Per member the restart
+        with the largest log marginal likelihood among the successful ones (status 0 or max |gradient| < 1e-4, the rule of
+        `GaussianProcess.fit_model`) becomes its hyper-parameters, and the member is set up again; a member without a
+        successful restart keeps its hyper-parameters and warns.  Status per restart: 0 = max |gradient| <= gtol, 1 = maxiter,
+        2 = the line search found no decrease within 40 halvings or its step no longer changes the objective in floating point
+        (with many training points the central-difference gradient cannot be driven below about 1e-6: such a run ends here, and
+        counts as successful by the rule above), 3 = the start point itself is not positive definite.  `fit_stats`: per member the arrays `lml`, `max_gradient`,
+        `iterations`, `evaluations`, `status` [R], `theta` (logarithms of the free hyper-parameters where the restart ended) and
+        `gradient` (d LML / d theta there) [R, n_free] over its restarts, and `chosen` [G] (-1 = none).
+        The device fits noise variance and kernel hyper-parameters ('fixed' ones stay); hyper-priors, boxed bounds and free
+        hyper-parameters of the mean are refused with NotImplementedError - `GaussianProcess.fit_model` of the member does them."""
+        import warnings
+        members = self._members()
+        problems = [self._fit_problem(g, gp) for g, gp in enumerate(members)]
+        thetas = self._start_points(problems, n_restarts, starts, seed, spread)
+        res = self._launch(problems, thetas, gtol, maxiter)
+        stats = {k: [] for k in ('lml', 'max_gradient', 'iterations', 'evaluations', 'status', 'theta', 'gradient')}
+        chosen = np.full(self._n_gps, -1, dtype=int)
+        for g, (gp, pb, r) in enumerate(zip(members, problems, res)):
+            with np.errstate(invalid='ignore'):
+                gmax = np.max(np.abs(r['grad']), axis=1)
+            ok = (r['status'] != 3) & np.isfinite(r['lml']) & ((r['status'] == 0) | (gmax < 1e-4))
+            stats['lml'].append(r['lml'])
+            stats['max_gradient'].append(gmax)
+            stats['theta'].append(r['theta'])
+            stats['gradient'].append(r['grad'])
+            for k in ('iterations', 'evaluations', 'status'):
+                stats[k].append(r[k])
+            if ok.any():
+                best = int(np.flatnonzero(ok)[np.argmax(r['lml'][ok])])
+                chosen[g] = best
+                full = np.exp(pb['theta_all'])
+                full[pb['free']] = np.exp(r['theta'][best])
+                gp._set_hyperparameters(full)
+                gp.setup(device_index=gp._dev.index)
+                gp._optimization_stats = {'success': True, 'message': FIT_STATUS[int(r['status'][best])],
+                                          'iter_count': int(r['iterations'][best]), 'max_gradient': float(gmax[best]),
+                                          'fun': float(-r['lml'][best])}
+            else:
+                msg = '; '.join(sorted({FIT_STATUS.get(int(s), str(s)) for s in r['status']}))
+                gp._optimization_stats = {'success': False, 'message': msg, 'iter_count': int(np.max(r['iterations'])),
+                                          'max_gradient': float(np.nanmin(gmax)) if np.isfinite(gmax).any() else np.nan, 'fun': np.nan}
+                warnings.warn(f"Fitting of GP didn't terminate successfully\nSolver message: {msg}\n"
+                              f"Try to use a different solver")
+        stats['chosen'] = chosen
+        self.fit_stats = stats
+        return self

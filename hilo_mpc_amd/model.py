@@ -615,6 +615,9 @@ class Model:
         variables (:3056-3061).  The device zoo offers this for the growth rate `mu` of 'chemostat4' over the
         features (S, I) (`nmpc_hybrid_bio.ipynb`); the GP must be trained (`setup` + `fit_model` or `set_training_data`
         + `setup`) with a squared-exponential kernel and a constant/zero mean."""
+        from .gp import GPArray
+        if isinstance(obj, GPArray):                     # like the list of its members
+            obj = list(obj._members())
         if isinstance(obj, (list, tuple, set)):
             for o in obj:
                 self.substitute_from(o)

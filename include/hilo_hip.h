@@ -515,6 +515,51 @@ int hilo_gp_kernel_matrix(int device, int nf, const double* kprog_host, int kpro
 int hilo_gp_mean(int device, int nf, const double* mprog_host, int mprog_len, int64_t n, const double* X,
                  double* mu, void* stream);
 
+/* Hyper-parameter fits of many GPs in ONE launch (GPArray.fit_model): a problem is one training set with one start point, one
+   workgroup maximises its log marginal likelihood (inference.py:210) by BFGS with Armijo backtracking entirely on the device.
+   theta = logarithms of the free hyper-parameter values, theta[0] = log(noise variance).  The device rebuilds the kernel
+   program from theta through the slot map: program[slot] = exp(coef * theta[index]) (HILO_GPFIT_EXP) or coef * theta[index]
+   (HILO_GPFIT_LIN); every other entry keeps the value of `kprog`.  The mean program is evaluated as given.
+   Limits: n <= HILO_GPFIT_MAX_N, n_theta <= HILO_GPFIT_MAX_THETA, kprog_len <= HILO_GPFIT_MAX_PROG, n_map <= HILO_GPFIT_MAX_MAP
+   (HILO_ENOTSUP beyond them); the device workspace is 2 n^2 doubles per problem (HILO_ENOMEM with the byte count when it does not
+   fit).  All pointers are HOST pointers. */
+#define HILO_GPFIT_EXP 0
+#define HILO_GPFIT_LIN 1
+#define HILO_GPFIT_MAX_N 256
+#define HILO_GPFIT_MAX_THETA 16
+#define HILO_GPFIT_MAX_PROG 256
+#define HILO_GPFIT_MAX_MAP 64
+/* status per problem */
+#define HILO_GPFIT_CONVERGED 0     /* max |d LML / d theta| <= gtol */
+#define HILO_GPFIT_MAXITER 1
+#define HILO_GPFIT_LINESEARCH 2    /* no decrease within 40 halvings, or step * g.d no longer changes the objective's value */
+#define HILO_GPFIT_START_NOT_PD 3  /* K + sn2 I at theta0 not positive definite or LML not finite: only the status is written */
+typedef struct hilo_gp_fit_problem {
+  int32_t nf, n;                 /* X is feature-major [nf][n] */
+  int32_t kprog_len, mprog_len;
+  int32_t n_theta, n_map;
+  const double* X;               /* [nf][n] */
+  const double* y;               /* [n] */
+  const double* kprog;           /* [kprog_len] kernel program at any admissible hyper-parameters (the fixed ones count) */
+  const double* mprog;           /* [mprog_len] */
+  const int32_t* map_slot;       /* [n_map] index into kprog of a parameter entry */
+  const int32_t* map_theta;      /* [n_map] index into theta */
+  const int32_t* map_kind;       /* [n_map] HILO_GPFIT_EXP / HILO_GPFIT_LIN */
+  const double* map_coef;        /* [n_map] */
+  const double* theta0;          /* [n_theta] start point */
+} hilo_gp_fit_problem;
+typedef struct hilo_gp_fit_opts {
+  int32_t maxiter;               /* 0 = evaluate only: LML and gradient at theta0 */
+  int32_t reserved;
+  double gtol;
+} hilo_gp_fit_opts;
+/* theta_out, grad_out: [n_problems][HILO_GPFIT_MAX_THETA] (the first n_theta entries of a row are written; grad = d LML / d theta at
+   theta_out); lml_out, iters_out, nfev_out, status_out: [n_problems].  A problem's result does not depend on the batch it runs
+   in nor on its position (fixed reduction order, no atomics). */
+int hilo_gp_fit_batch(int device, int n_problems, const hilo_gp_fit_problem* problems, const hilo_gp_fit_opts* options,
+                      double* theta_out, double* lml_out, double* grad_out, int32_t* iters_out, int32_t* nfev_out,
+                      int32_t* status_out, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------- */
 /* NMPC: batched direct multiple shooting + interior point                                                  */
 /* replaces `ca.nlpsol('solver','ipopt',{'f','x','p','g'})` built at hilo_mpc/modules/controller/mpc.py:      */
